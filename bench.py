@@ -3,7 +3,7 @@ Headline benchmark: patches/sec through one training step = 200-iteration
 FISTA inference + one dictionary update, 16x16 patches (n=256), 1024-atom
 dictionary (BASELINE.json configs[1]; configs[2] when launched on N GPUs).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -16,6 +16,14 @@ scaling: --batch patches per GPU); inference is rank-local; the un-normalised
 dictionary gradient is summed with one RCCL all-reduce per step.  Rank 0 prints
 ONE JSON line.  Inputs are synthetic (numpy RandomState) and resident in HBM
 before the timed region starts.
+
+A plain run sets up, warms up, times --steps steps and prints the line (with
+`roofline`, read from the HIP events of the timed steps).  --full adds what
+takes runs of its own: the other fused precisions under `modes` and the CPU
+oracle under `cpu_baseline`.  --dump-outputs DIR writes what the last timed
+step returned, before anything else runs: DIR/dictionary.npy (the updated
+(1024, 256) dictionary) and DIR/codes_sample.npy (rank 0's codes at
+DUMP_CODE_ROWS rows drawn with seed DUMP_SEED, in ascending row order).
 """
 import argparse
 import json
@@ -36,6 +44,8 @@ FISTA_ITERS = 200
 LAMBDA = 0.008       # examples/train_sparse_coding.py:59 of the reference
 DICT_STEP = 0.1
 FLOP_PER_PATCH_ITER = 4 * N_ATOMS * N_PIX     # two contractions of 2*s*n
+DUMP_CODE_ROWS = 4096  # 16 MiB of float32 codes
+DUMP_SEED = 2024
 
 # peaks from /opt/skills/guides/MI355X_MICROARCH.md (dense, no sparsity)
 PEAK_TFLOPS = {'bf16': 2500.0, 'bf16x3': 2500.0, 'f16x3': 2500.0,
@@ -62,10 +72,34 @@ def parse_args():
                   help='patches per GPU (0 = default for the precision)')
   ap.add_argument('--precision', default='auto',
                   choices=['auto', 'f32', 'f16x3', 'bf16x3', 'bf16'])
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also time the other fused precisions (modes) and the '
+                       'CPU oracle (cpu_baseline)')
+  ap.add_argument('--dump-outputs', metavar='DIR',
+                  help='write the outputs of the last timed step as '
+                       'DIR/<name>.npy')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='with --full: skip the CPU oracle')
   ap.add_argument('--cpu-sample', type=int, default=4096,
                   help='patches in the CPU-baseline sample')
-  return ap.parse_args()
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
+  return args
+
+
+def dump_outputs(out_dir, codes, dictionary):
+  """The arrays the timed path hands its caller: the codes of the last step
+  (a fixed seeded sample of rows; the full (batch, 1024) array is 512 MiB)
+  and the dictionary it updated in place."""
+  rows = np.sort(np.random.RandomState(DUMP_SEED).choice(
+      codes.shape[0], min(DUMP_CODE_ROWS, codes.shape[0]), replace=False))
+  index = torch.from_numpy(rows).to(codes.device)
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, 'codes_sample.npy'),
+          codes.index_select(0, index).float().cpu().numpy())
+  np.save(os.path.join(out_dir, 'dictionary.npy'),
+          dictionary.float().cpu().numpy())
 
 
 def synthetic_inputs(rank, batch, device):
@@ -214,10 +248,15 @@ def main():
   vtc_hip.kernel_timing = inference_ms = []
   t0 = time.perf_counter()
   for _ in range(args.steps):
-    step()
+    codes = None     # released before the next step allocates its own
+    codes = step()
   fence()
   elapsed = time.perf_counter() - t0
   vtc_hip.kernel_timing = None
+  if args.dump_outputs and rank == 0:
+    # before --full runs more steps on D
+    dump_outputs(args.dump_outputs, codes, D)
+  del codes
   if dist.is_initialized():
     worst = torch.tensor([elapsed], dtype=torch.float64, device=device)
     dist.all_reduce(worst, op=dist.ReduceOp.MAX)
@@ -279,7 +318,8 @@ def main():
                   'iteration and an eight-wave form were built and measured '
                   'slower / equal (profiles/r03_fused_onepacking.txt)'},
   }
-  if world == 1 and precision != 'bf16' and ista_fista.fused_available():
+  if (args.full and world == 1 and precision != 'bf16'
+      and ista_fista.fused_available()):
     # the other fused modes on the same inputs, reported beside the headline:
     # bf16x3 (1.75e-5 from the reference at T = 200, outside north_star's 1e-5)
     # and the bf16 fast mode (~1e-2): never `value`
@@ -320,8 +360,9 @@ def main():
   if rank == 0:
     # rank 0's host cores, for every N (the other ranks wait at the barrier
     # below); roofline stays per GPU
-    result['cpu_baseline'] = (None if args.no_cpu_baseline
-                              else cpu_baseline(args.cpu_sample))
+    result['cpu_baseline'] = (cpu_baseline(args.cpu_sample)
+                              if args.full and not args.no_cpu_baseline
+                              else None)
     print(json.dumps(result))
   if dist.is_initialized():
     dist.barrier()

@@ -201,6 +201,33 @@ def test_bench_refuses_a_mismatched_launcher_and_spawns_without_one():
   assert len(set(e['MASTER_PORT'] for e in launched)) == 1
 
 
+def test_bench_dumps_a_fixed_sample_of_the_last_step(tmp_path):
+  """bench.py --dump-outputs: float32 .npy files, the same codes rows on every
+  run, the dictionary whole, well under 64 MB."""
+  import importlib.util
+  repo = os.path.join(os.path.dirname(__file__), '..')
+  spec = importlib.util.spec_from_file_location(
+      'bench_module', os.path.join(repo, 'bench.py'))
+  bench = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(bench)
+  codes = torch.arange(20000 * 8, dtype=torch.float32).reshape(20000, 8)
+  dictionary = torch.from_numpy(helpers.unit_rows(3, 16, 8))
+  for run in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / run), codes, dictionary)
+  assert sorted(os.listdir(tmp_path / 'a')) == ['codes_sample.npy',
+                                                'dictionary.npy']
+  sample = np.load(tmp_path / 'a' / 'codes_sample.npy')
+  assert sample.dtype == np.float32
+  assert sample.shape == (bench.DUMP_CODE_ROWS, 8)
+  rows = sample[:, 0] / 8
+  assert (np.diff(rows) > 0).all() and rows.max() < 20000
+  assert np.array_equal(sample, np.load(tmp_path / 'b' / 'codes_sample.npy'))
+  assert np.array_equal(np.load(tmp_path / 'a' / 'dictionary.npy'),
+                        dictionary.numpy())
+  assert bench.DUMP_CODE_ROWS * bench.N_ATOMS * 4 + \
+      bench.N_ATOMS * bench.N_PIX * 4 < 64e6
+
+
 def test_data_parallel_update_matches_single_process(tmp_path):
   """Shard a batch over 2 gloo ranks: summed shard gradients / global batch
   reproduce the full-batch update, and both ranks end bit-identical."""

@@ -6,9 +6,9 @@ tag=${1:-r03}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-echo "== bench" && timeout -k 10 400 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err; tail -c 600 $out/bench_default.json
+echo "== bench" && timeout -k 10 400 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err; tail -c 600 $out/bench_default.json
 echo "== kernel stats of the bench step"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_stats -o b -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_stats.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_stats -o b -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_stats.log 2>&1
 cp $out/bench_stats/b_kernel_stats.csv $out/bench_kernel_stats.csv 2>/dev/null
 run_pmc() {  # name, counters..., then -- command
   name=$1; shift
