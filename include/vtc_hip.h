@@ -26,6 +26,9 @@
  *     and extraction)                                                 -> vtc_standardize_data_range, vtc_whiten_center_surround,
  *                                                                        vtc_draw_patch_positions, vtc_extract_patches
  *   dict_update_rules/fully_connected/ica_natural_gradient.py:6-35    -> vtc_ica_moment, vtc_ica_apply
+ *   utils/image_processing.py:338-460 (whiten_ZCA, unwhiten_ZCA),
+ *     training/pca.py:8-39                                            -> vtc_column_covariance, vtc_sym_eig,
+ *                                                                        vtc_zca_matrices, vtc_row_transform
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to contiguous row-major float32 unless
@@ -374,6 +377,51 @@ size_t vtc_ica_apply_workspace_bytes(int64_t s, int64_t n);
 int vtc_ica_apply(float* dictionary, const float* moment_sum,
                   int64_t global_batch, int64_t s, int64_t n, float stepsize,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- ZCA whitening and PCA (utils/image_processing.py:338-460,
+ * training/pca.py:8-39): covariance, symmetric eigen-decomposition, the two
+ * ZCA matrices and the row transform that applies them. */
+size_t vtc_column_covariance_workspace_bytes(int64_t rows, int64_t cols);
+/* x (rows, cols) float32.  cov_f64 (cols, cols) = Xc^T Xc / rows in float64
+ * (products and sums in float64; row slabs summed in a fixed order, so the
+ * result is bitwise reproducible and exactly symmetric), Xc = x - mean when
+ * center != 0, Xc = x otherwise.  means_f64 (cols doubles) and
+ * grand_mean_f64 (1 double, the mean of the column means) are optional
+ * outputs (NULL: not written); the column means are computed whenever one of
+ * them is asked for or center != 0.  cov_f64 may be NULL when one of the
+ * other two is given: the means alone.  cols <= 46340. */
+int vtc_column_covariance(const float* x, int64_t rows, int64_t cols,
+                          int center, double* means_f64,
+                          double* grand_mean_f64, double* cov_f64,
+                          void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* Eigen-decomposition of a symmetric (n, n) float64 matrix (only the upper
+ * triangle is read), n <= 256: parallel-ordered two-sided Jacobi in float64
+ * in one workgroup, at most max_sweeps sweeps, stopped once the off-diagonal
+ * Frobenius norm is <= 1e-14 of the whole.  eigvals_f64 (n) in descending
+ * order; eigvecs_f32 (n, n) holds the eigenvectors as COLUMNS in the same
+ * order, each signed so that its largest-magnitude float32 component is
+ * positive (ties: the lower index).  status (device, 2 ints) = [converged
+ * (1 / 0), sweeps run].  n > 256: VTC_ERR_UNSUPPORTED (the caller then uses a
+ * library eigen-solver). */
+size_t vtc_sym_eig_workspace_bytes(int64_t n);
+int vtc_sym_eig(const double* a_f64, int64_t n, int max_sweeps,
+                double* eigvals_f64, float* eigvecs_f32, int* status,
+                void* workspace, size_t workspace_bytes, void* stream);
+/* From eigenvector columns U (n, n) float32 and eigenvalues w (n) float64:
+ * w_f32 = U diag(1 / (sqrt(w) + eps)) U^T and w_inv_f32 = U diag(sqrt(w) +
+ * eps) U^T, summed in float64 and rounded to float32 (negative w count as
+ * 0).  Either output may be NULL, not both.  n <= 4096. */
+int vtc_zca_matrices(const float* eigvecs_f32, const double* eigvals_f64,
+                     int64_t n, double eps, float* w_f32, float* w_inv_f32,
+                     void* stream);
+/* y (rows, n) = (x - offsets) m + add: x (rows, n), offsets (n) subtracted
+ * from every row before the product (in float32, as the reference centres
+ * its data), m (n, n), add a scalar; float32 FMA chains in k order.
+ * n <= 4096, any rows. */
+int vtc_row_transform(const float* x, int64_t rows, int64_t n,
+                      const float* offsets, const float* m, float add,
+                      float* y, void* stream);
 
 #ifdef __cplusplus
 }

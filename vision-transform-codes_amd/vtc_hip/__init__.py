@@ -126,6 +126,14 @@ SIGNATURES = {
     'vtc_code_energy_workspace_bytes': (_sz, [_i64, _i64, _i64]),
     'vtc_code_energy': (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     'vtc_hessian_ema': (_i32, [_vp, _vp, _i64, _i64, _vp]),
+    'vtc_column_covariance_workspace_bytes': (_sz, [_i64, _i64]),
+    'vtc_column_covariance': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp,
+                                     _vp, _sz, _vp]),
+    'vtc_sym_eig_workspace_bytes': (_sz, [_i64]),
+    'vtc_sym_eig': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vtc_zca_matrices': (_i32, [_vp, _vp, _i64, ctypes.c_double, _vp, _vp,
+                                _vp]),
+    'vtc_row_transform': (_i32, [_vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp]),
 }
 
 
