@@ -430,6 +430,147 @@ def make_conv_long(ref):
   np.savez_compressed(GOLDEN / 'conv_long.npz', **out)
 
 
+# rows of the configs[3] batch whose codes subspace_c3.npz keeps: both ends of
+# the full 32-patch tile, both ends of the partial one, and rows in between
+C3_ROWS = (0, 9, 18, 31, 32, 39, 44, 47)
+# groups whose updated dictionary rows it keeps: every 16th of the 512
+C3_GROUP_STEP = 16
+
+
+def make_subspace_c3(ref):
+  """BASELINE configs[3] at full dictionary size: 4096 atoms in 512 groups of
+  8, 16x16 patches, lambda 0.008, b = 48 (one full 32-patch tile of the
+  streamed kernel and one partial tile).  Inputs are regenerated from their
+  seeds by the tests.
+
+  Stored: the step from the reference's own eigen-solve of the grouped
+  dictionary (subspace_ista_fista.py:115-123), the reference's FISTA codes at
+  T = 1, 20, 200, ISTA codes at T = 50 and a FISTA warm start of 20
+  iterations from the T = 20 codes (all at that step), float64 oracle
+  codes at T = 200 at the same step, and one subspace cheap-quadratic update
+  (penalty 2e-4, stepsize 0.1, Hessian diagonal from the trainer's EMA at
+  step 0) from the T = 200 codes of the kept rows.
+
+  Codes are dense here (every group survives), so a full (48, 4096) array is
+  768 KiB; to stay under 1 MiB per file the codes keep the rows C3_ROWS only
+  (all 4096 columns: every slot of every group) and the update keeps the
+  rows of every C3_GROUP_STEP-th group, plus float64 row sums of all 4096
+  updated rows.  Rows of the batch are independent, so a test runs all 48 and
+  compares these."""
+  seeds = (80, 81)
+  X = gaussian_patches(seeds[0], 48, 256)
+  D = unit_rows(seeds[1], 4096, 256)
+  groups = [list(map(int, g)) for g in np.array_split(np.arange(4096), 512)]
+  lam = 0.008
+  rows = np.array(C3_ROWS, np.int64)
+  # the reference's step: grouped dictionary as :94-111 builds it, then the
+  # eigen-solve of :115-123 (torch.symeig -> eigvalsh, import_reference)
+  Dg = torch.zeros(8 * 512, 256)
+  for g_idx, members in enumerate(groups):
+    Dg[8 * g_idx:8 * g_idx + len(members)] = T(D)[members]
+  eta = 1. / torch.symeig(torch.mm(Dg.t(), Dg))[0][-1]
+  out = {'seed_images': np.int64(seeds[0]),
+         'seed_dictionary': np.int64(seeds[1]),
+         'rows': rows, 'sparsity_weight': np.float32(lam),
+         'stepsize': np.float32(eta),
+         'images_sum': np.float64(X.astype(np.float64).sum()),
+         'dictionary_sum': np.float64(D.astype(np.float64).sum())}
+  mine_eta = 1. / sc_oracle.largest_eigenvalue(
+      torch.mm(sc_oracle.grouped_dictionary(T(D), groups).t(),
+               sc_oracle.grouped_dictionary(T(D), groups)))
+  print('   reference eta %.9g  oracle eta %.9g' % (float(eta), float(mine_eta)))
+  assert float(eta) == float(mine_eta)
+  traced = trace_reference(ref.sub_inf.run, [1, 20, 200], images=T(X),
+                           dictionary=T(D), group_assignments=groups,
+                           sparsity_weight=lam, variant='fista')
+  _, mine_trace = sc_oracle.subspace_ista_fista(T(X), T(D), groups, lam, 200,
+                                                trace_at=[1, 20, 200])
+  for k, codes in traced.items():
+    report('subspace_c3 fista T=%d' % k, mine_trace[k], codes)
+    out['codes_fista_T%d' % k] = codes.numpy()[rows]
+  codes = ref.sub_inf.run(T(X), T(D), groups, lam, 50, variant='ista')
+  report('subspace_c3 ista T=50',
+         sc_oracle.subspace_ista_fista(T(X), T(D), groups, lam, 50,
+                                       variant='ista'), codes)
+  out['codes_ista_T50'] = codes.numpy()[rows]
+  # warm start from the T = 20 codes, 20 more FISTA iterations
+  warm = ref.sub_inf.run(T(X), T(D), groups, lam, 20, variant='fista',
+                         initial_codes=traced[20])
+  report('subspace_c3 warm start',
+         sc_oracle.subspace_ista_fista(T(X), T(D), groups, lam, 20,
+                                       initial_codes=traced[20]), warm)
+  out['codes_fista_warm20'] = warm.numpy()[rows]
+  # float64 oracle at the reference's step: what the float32 arithmetic of
+  # either side would give without rounding
+  truth = sc_oracle.subspace_ista_fista(T(X).double(), T(D).double(), groups,
+                                        lam, 200, stepsize=float(eta))
+  report('subspace_c3 fp64-oracle vs fp32-reference', truth.float(),
+         traced[200])
+  out['codes_fista_T200_fp64'] = truth.numpy()[rows]
+  # the update is taken on the kept rows of the batch (its inputs must be in
+  # the file): the full 4096 x 256 dictionary, 8 patches
+  C = traced[200][rows]
+  Xr = T(X[rows])
+  h = torch.zeros(4096)
+  h.mul_(0.99).add_(torch.pow(C, 2).mean(0) / 100)   # trainer's EMA, step 0
+  report('subspace_c3 hessian ema',
+         sc_oracle.hessian_diag_ema_(torch.zeros(4096), C), h)
+  out['hessian_diagonal'] = h.numpy()
+  Dn = T(D.copy())
+  ref.sub_cq.run(Xr, Dn, C, groups, h, 2e-4, stepsize=0.1)
+  Dm = T(D.copy())
+  sc_oracle.subspace_cheap_quadratic_descent(Xr, Dm, C, groups, h, 2e-4,
+                                             stepsize=0.1)
+  report('subspace_c3 cheap-quad', Dm, Dn)
+  kept = np.concatenate([groups[g] for g in range(0, 512, C3_GROUP_STEP)])
+  out['dict_rows'] = kept.astype(np.int64)
+  out['dict_after_cheapquad_rows'] = Dn.numpy()[kept]
+  out['dict_after_cheapquad_rowsum'] = Dn.numpy().astype(np.float64).sum(
+      axis=1)
+  np.savez_compressed(GOLDEN / 'subspace_c3.npz', **out)
+
+
+def make_conv_c4(ref):
+  """BASELINE configs[4] kernel bank (128 kernels of 11x11, stride 1) in the
+  convergent regime (near-delta kernels, see near_delta_kernels) on one 40x40
+  image padded as the reference pads it: the reference's FISTA codes at
+  T = 20, 100, 200 with its own step, which is stored, and float64 oracle
+  codes at T = 200 at that step, stored as float32."""
+  img, k, s = 40, 11, 128
+  lead, trail = ref.conv_utils.get_padding_amt(img, k, 1)
+  padded = img + lead + trail
+  rs = np.random.RandomState(90)
+  imgs = np.zeros((1, 1, padded, padded), np.float32)
+  imgs[:, :, lead:lead + img, lead:lead + img] = (
+      0.5 * rs.randn(1, 1, img, img)).astype(np.float32)
+  D = near_delta_kernels(91, s, k, 0.02)
+  stride, pad = (1, 1), ((lead, trail), (lead, trail))
+  lam = 0.05
+  F = T(D.reshape(s, -1))
+  eta = 1. / torch.symeig(torch.mm(F, F.t()))[0][-1]
+  assert float(eta) == float(sc_oracle.conv_stepsize(T(D)))
+  out = {'images_padded': imgs, 'dictionary': D, 'stride': np.array(stride),
+         'padding': np.array(pad), 'sparsity_weight': np.float32(lam),
+         'stepsize': np.float32(eta)}
+  traced = trace_reference(ref.conv_inf.run, [20, 100, 200],
+                           images_padded=T(imgs), dictionary=T(D),
+                           kernel_stride=stride, padding_dims=pad,
+                           sparsity_weight=lam, variant='fista')
+  _, mine_trace = sc_oracle.conv_ista_fista(T(imgs), T(D), stride, pad, lam,
+                                            200, trace_at=[20, 100, 200])
+  for iters, codes in traced.items():
+    assert bool(torch.isfinite(codes).all())
+    report('conv_c4 fista T=%d' % iters, mine_trace[iters], codes)
+    out['codes_fista_T%d' % iters] = codes.numpy()
+  truth = sc_oracle.conv_ista_fista(T(imgs).double(), T(D).double(), stride,
+                                    pad, lam, 200, stepsize=float(eta))
+  report('conv_c4 fp64-oracle vs fp32-reference', truth.float(), traced[200])
+  out['codes_fista_T200_fp64'] = truth.float().numpy()
+  print('   conv_c4 non-zero fraction at T=200: %.4f'
+        % float((traced[200] != 0).float().mean()))
+  np.savez_compressed(GOLDEN / 'conv_c4.npz', **out)
+
+
 class _ListDataset(torch.utils.data.Dataset):
   def __init__(self, tensor):
     self.tensor = tensor
@@ -814,6 +955,7 @@ def make_whitened(ref):
 MAKERS = {'fc_c1': make_fc_c1, 'fc_c2_mini': make_fc_c2_mini,
           'subspace': make_subspace, 'conv': make_conv,
           'conv_long': make_conv_long,
+          'subspace_c3': make_subspace_c3, 'conv_c4': make_conv_c4,
           'trainer': make_trainer, 'trainer_c2': make_trainer_c2, 'reset_prune': make_reset_prune,
           'whitened': make_whitened,
           'metrics': make_metrics, 'ica': make_ica}

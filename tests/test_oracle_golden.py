@@ -185,6 +185,67 @@ def test_conv_long_horizon_golden():
           codes.numpy(), g['%s_codes_fista_T%d' % (name, iters)]) < 1e-6
 
 
+def test_subspace_c3_golden():
+  """configs[3] fixture: the regenerated inputs are the ones it was made
+  from, and the oracle reproduces the reference's step, its stored rows at
+  T = 1 and 20, and the cheap-quadratic update of those rows."""
+  g = helpers.load('subspace_c3')
+  X = helpers.gaussian_patches(int(g['seed_images']), 48, 256)
+  Dn = helpers.unit_rows(int(g['seed_dictionary']), 4096, 256)
+  assert abs(X.astype(np.float64).sum() - float(g['images_sum'])) < 1e-9
+  assert abs(Dn.astype(np.float64).sum() - float(g['dictionary_sum'])) < 1e-9
+  groups = [list(map(int, x)) for x in np.array_split(np.arange(4096), 512)]
+  rows = g['rows']
+  assert rows.shape == (8,) and rows.max() == 47 and 31 in rows and 32 in rows
+  X, D = T(X), T(Dn)
+  eta = sc_oracle.largest_eigenvalue(torch.mm(D.t(), D))
+  assert abs(1. / float(eta) - float(g['stepsize'])) < 1e-6 * float(
+      g['stepsize'])
+  lam = float(g['sparsity_weight'])
+  _, trace = sc_oracle.subspace_ista_fista(X, D, groups, lam, 20,
+                                           stepsize=float(g['stepsize']),
+                                           trace_at=[1, 20])
+  for k in (1, 20):
+    helpers.assert_codes_match(trace[k].numpy()[rows],
+                               g['codes_fista_T%d' % k],
+                               helpers.REL_TOL_SHORT, 'T=%d' % k)
+  # the float64 record is within the reference's float32 noise of its codes
+  floor = helpers.rel_err(g['codes_fista_T200'], g['codes_fista_T200_fp64'])
+  assert 1e-6 < floor < helpers.REL_TOL_F32
+  C = T(g['codes_fista_T200'])
+  h = sc_oracle.hessian_diag_ema_(torch.zeros(4096), C)
+  assert helpers.rel_err(h.numpy(), g['hessian_diagonal']) < 1e-6
+  D1 = T(Dn.copy())
+  sc_oracle.subspace_cheap_quadratic_descent(X[rows], D1, C, groups,
+                                             T(g['hessian_diagonal']), 2e-4,
+                                             stepsize=0.1)
+  assert helpers.rel_err(D1.numpy()[g['dict_rows']],
+                         g['dict_after_cheapquad_rows']) < 1e-6
+  assert helpers.rel_err(D1.numpy().astype(np.float64).sum(axis=1),
+                         g['dict_after_cheapquad_rowsum']) < 1e-6
+
+
+def test_conv_c4_golden():
+  """configs[4] fixture: the reference's padding and step, and the oracle
+  follows its codes to T = 20."""
+  g = helpers.load('conv_c4')
+  imgs, D = T(g['images_padded']), T(g['dictionary'])
+  assert tuple(D.shape) == (128, 1, 11, 11)
+  lead, trail = sc_oracle.conv_padding_amount(40, 11, 1)
+  assert tuple(imgs.shape) == (1, 1, 40 + lead + trail, 40 + lead + trail)
+  pad = tuple(tuple(int(v) for v in row) for row in g['padding'])
+  assert pad == ((lead, trail), (lead, trail))
+  assert abs(float(sc_oracle.conv_stepsize(D)) -
+             float(g['stepsize'])) < 1e-7
+  codes = sc_oracle.conv_ista_fista(imgs, D, (1, 1), pad,
+                                    float(g['sparsity_weight']), 20)
+  # (1.7e-6 with another thread count than the fixture's: the near-delta
+  # bank is ill-conditioned enough for the convolutions' summation order to
+  # show this early)
+  helpers.assert_codes_match(codes.numpy(), g['codes_fista_T20'],
+                             helpers.REL_TOL_SHORT, 'conv_c4 T=20')
+
+
 def test_conv_geometry_matches_config5():
   # SURVEY.md section 8: 256 px, 11x11 kernels, stride 1 -> pad (10,10),
   # padded 276, code map 266

@@ -28,13 +28,13 @@ def test_ragged_overlapping_groups(device, plugins):
   for variant in ('ista', 'fista'):
     codes = sub.run(X, D, RAGGED, 0.02, 30, variant=variant)
     helpers.assert_codes_match(codes.cpu().numpy(), g['ro_codes_' + variant],
-                               2e-5, 'ragged ' + variant, max_flip_mag=1e-5)
+                               helpers.REL_TOL_SHORT, 'ragged ' + variant)
   init = helpers.to_dev(g['ro_codes_ista'], device)
   keep = init.clone()
   warm = sub.run(X, D, RAGGED, 0.02, 10, initial_codes=init)
   assert torch.equal(init, keep)
-  helpers.assert_codes_match(warm.cpu().numpy(), g['ro_codes_warm'], 2e-5,
-                             'ragged warm', max_flip_mag=1e-5)
+  helpers.assert_codes_match(warm.cpu().numpy(), g['ro_codes_warm'],
+                             helpers.REL_TOL_SHORT, 'ragged warm')
 
 
 def test_groups_of_four_and_mini_c4(device, plugins):
@@ -43,14 +43,14 @@ def test_groups_of_four_and_mini_c4(device, plugins):
   X = helpers.to_dev(g['g4_images'], device)
   D = helpers.to_dev(g['g4_dictionary'], device)
   codes = sub.run(X, D, GROUPS4, 0.02, 40)
-  helpers.assert_codes_match(codes.cpu().numpy(), g['g4_codes_fista'], 2e-5,
-                             'groups of 4', max_flip_mag=1e-5)
+  helpers.assert_codes_match(codes.cpu().numpy(), g['g4_codes_fista'],
+                             helpers.REL_TOL_SHORT, 'groups of 4')
   X = helpers.to_dev(helpers.gaussian_patches(24, 32, 256), device)
   D = helpers.to_dev(helpers.unit_rows(25, 512, 256), device)
   groups = [list(map(int, x)) for x in np.array_split(np.arange(512), 64)]
   codes = sub.run(X, D, groups, 0.008, 50)
-  helpers.assert_codes_match(codes.cpu().numpy(), g['c4_codes_fista'], 2e-5,
-                             'mini config 4', max_flip_mag=1e-5)
+  helpers.assert_codes_match(codes.cpu().numpy(), g['c4_codes_fista'],
+                             helpers.REL_TOL_SHORT, 'mini config 4')
 
 
 def test_early_stopping_and_unsupported_options(device, plugins):
@@ -60,14 +60,19 @@ def test_early_stopping_and_unsupported_options(device, plugins):
   D = helpers.to_dev(g['g4_dictionary'], device)
   Xc, Dc = torch.from_numpy(g['g4_images']), torch.from_numpy(
       g['g4_dictionary'])
-  ref = sc_oracle.subspace_ista_fista(Xc, Dc, GROUPS4, 0.02, 400,
-                                      variant='ista',
-                                      early_stopping_epsilon=5e-3)
+  # the oracle's trace holds one entry per iteration it ran
+  ref, trace = sc_oracle.subspace_ista_fista(Xc, Dc, GROUPS4, 0.02, 400,
+                                             variant='ista',
+                                             early_stopping_epsilon=5e-3,
+                                             trace_at=set(range(1, 401)))
   codes = sub.run(X, D, GROUPS4, 0.02, 400, variant='ista',
                   early_stopping_epsilon=5e-3)
   assert 1 < sub.run.last_iters < 400
-  helpers.assert_codes_match(codes.cpu().numpy(), ref.numpy(), 1e-4,
-                             'early stop', max_flip_mag=1e-4)
+  assert sub.run.last_iters == len(trace)
+  err, flips = helpers.assert_codes_match(
+      codes.cpu().numpy(), ref.numpy(), helpers.REL_TOL_SHORT, 'early stop')
+  print('early stop after %d iterations: rel %.2e, %d flips' % (
+      sub.run.last_iters, err, flips))
   with pytest.raises(NotImplementedError):
     sub.run(X, D, GROUPS4, 0.02, 5, hard_threshold=True)
   with pytest.raises(NotImplementedError):
