@@ -29,6 +29,8 @@
  *   utils/image_processing.py:338-460 (whiten_ZCA, unwhiten_ZCA),
  *     training/pca.py:8-39                                            -> vtc_column_covariance, vtc_sym_eig,
  *                                                                        vtc_zca_matrices, vtc_row_transform
+ *   analysis_transforms/fully_connected/invertible_linear.py:6-28
+ *     (`torch.inverse(dictionary)`, training/ica.py:128-240)          -> vtc_mat_inverse (+ vtc_row_transform)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to contiguous row-major float32 unless
@@ -422,6 +424,25 @@ int vtc_zca_matrices(const float* eigvecs_f32, const double* eigvals_f64,
 int vtc_row_transform(const float* x, int64_t rows, int64_t n,
                       const float* offsets, const float* m, float add,
                       float* y, void* stream);
+
+/* ---- matrix inverse (invertible_linear.py: codes = images @
+ * torch.inverse(dictionary)) ----
+ * a (n, n) float32 row-major -> a_inv (n, n) float32, which must not alias a.
+ * LU factorisation with partial pivoting in float64 (pivot: the largest
+ * |value| of the column, ties to the lower row), the inverse from the
+ * triangular solves against the identity, rounded once to float32.  Every sum
+ * runs in a fixed order: two calls give bitwise identical output.
+ * status (device, 2 ints) = [nonsingular (1 / 0), index of the first bad
+ * pivot or -1]; a bad pivot is an exact 0 or a non-finite value, so NaN or
+ * Inf input also gives nonsingular = 0 (with index -1 in the unlikely case
+ * that no pivot shows it).  The status is only written on the device; a_inv
+ * is then not meaningful.  1 <= n <= 256; n > 256: VTC_ERR_UNSUPPORTED (the
+ * caller then uses a library inverse).  Null pointers, n <= 0, aliasing and a
+ * workspace below vtc_mat_inverse_workspace_bytes(n) are refused before any
+ * HIP call. */
+size_t vtc_mat_inverse_workspace_bytes(int64_t n);
+int vtc_mat_inverse(const float* a, int64_t n, float* a_inv, int* status,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,8 @@ SIGNATURES = {
     'vtc_zca_matrices': (_i32, [_vp, _vp, _i64, ctypes.c_double, _vp, _vp,
                                 _vp]),
     'vtc_row_transform': (_i32, [_vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp]),
+    'vtc_mat_inverse_workspace_bytes': (_sz, [_i64]),
+    'vtc_mat_inverse': (_i32, [_vp, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

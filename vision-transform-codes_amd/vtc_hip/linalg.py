@@ -1,13 +1,17 @@
 """
 Covariance, symmetric eigen-decomposition and the ZCA row transform on the
 device (csrc/zca.hip): the primitives behind utils.image_processing.whiten_ZCA
-/ unwhiten_ZCA and training.pca.train_dictionary.
+/ unwhiten_ZCA and training.pca.train_dictionary; the matrix inverse
+(csrc/inverse.hip) behind analysis_transforms.fully_connected.
+invertible_linear and training.ica.
 
-Library routines stand in for a kernel of this engine in two documented places
-only, both in symmetric_eigh: matrices larger than 256 x 256 (beyond the
+Library routines stand in for a kernel of this engine in three documented
+places only.  In symmetric_eigh: matrices larger than 256 x 256 (beyond the
 single-workgroup Jacobi solver) and a Jacobi run that reports it did not
-converge within JACOBI_MAX_SWEEPS sweeps (with a warning).  Both take
-torch.linalg.eigh in float64 on the device.
+converge within JACOBI_MAX_SWEEPS sweeps (with a warning); both take
+torch.linalg.eigh in float64 on the device.  In mat_inverse / inverse:
+matrices larger than 256 x 256 take torch.linalg.inv_ex in float64 on the
+device.
 """
 import ctypes
 import warnings
@@ -128,3 +132,64 @@ def row_transform(x, offsets, matrix, add):
                               float(add), ptr(y), current_stream(x.device)),
         'vtc_row_transform')
   return y
+
+
+INVERSE_MAX_N = 256
+
+
+def mat_inverse(a, status=None):
+  """Inverse of an (n, n) float32 device matrix without a host
+  synchronisation.  Returns (a_inv (n, n) float32, status (2,) int32 device
+  tensor [nonsingular (1 / 0), first bad pivot index or -1]); `status` may be
+  given as a (2,) int32 device tensor to write into.
+
+  n <= 256: vtc_mat_inverse (float64 LU with partial pivoting, rounded once).
+  n > 256: torch.linalg.inv_ex in float64 on the device, rounded to float32;
+  the status then comes from its LU (and a finiteness check of the input)."""
+  a = require_device_tensor(a, 'a').contiguous()
+  if a.dim() != 2 or a.shape[0] != a.shape[1]:
+    raise ValueError('a must be a square matrix, got shape %s'
+                     % (tuple(a.shape),))
+  n = a.shape[0]
+  dev = a.device
+  if status is None:
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+  else:
+    status = require_device_tensor(status, 'status', torch.int32)
+    assert status.shape == (2,) and status.is_contiguous()
+  if n > INVERSE_MAX_N:
+    a_inv, info = torch.linalg.inv_ex(a.to(torch.float64))
+    good = (info == 0) & torch.isfinite(a).all()
+    status[0] = good.to(torch.int32)
+    status[1] = torch.where(info > 0, info - 1, -1).to(torch.int32)
+    return a_inv.to(torch.float32), status
+  lib = load_library()
+  a_inv = torch.empty_like(a)
+  ws = workspace(lib.vtc_mat_inverse_workspace_bytes(n), dev)
+  check(lib.vtc_mat_inverse(ptr(a), n, ptr(a_inv), ptr(status), ptr(ws),
+                            ws.numel(), current_stream(dev)),
+        'vtc_mat_inverse')
+  return a_inv, status
+
+
+def raise_if_singular(status, what='matrix'):
+  """One host read of a mat_inverse status; raises torch.linalg.LinAlgError
+  (what torch.inverse raises) for a singular or non-finite input."""
+  nonsingular, bad = [int(v) for v in status.tolist()]
+  if nonsingular != 1:
+    if bad >= 0:
+      raise torch.linalg.LinAlgError(
+          'inverse: the %s is singular (pivot %d is zero or not finite)'
+          % (what, bad))
+    raise torch.linalg.LinAlgError(
+        'inverse: the %s holds a non-finite value' % what)
+
+
+def inverse(a, check=True):
+  """a^-1 of an (n, n) float32 device matrix as float32 (mat_inverse).  With
+  check=True one host read of the status raises torch.linalg.LinAlgError for
+  a singular or non-finite input, as torch.inverse would."""
+  a_inv, status = mat_inverse(a)
+  if check:
+    raise_if_singular(status)
+  return a_inv
