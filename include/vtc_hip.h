@@ -239,7 +239,9 @@ int vtc_fc_dict_gradient(const float* images, const float* dictionary,
                          size_t workspace_bytes, void* stream);
 /* penalty_grad (s,n) = sum over groups of the |cos| alignment gradients
  * (subspace_sc_cheap_quadratic_descent.py:91-127); index/valid and the CSR
- * inverse map atom_ptr/atom_slots as above.  Groups of up to 32 atoms. */
+ * inverse map atom_ptr/atom_slots as above.  Groups of up to 256 atoms whose
+ * tile of (m*n + m*m + m) floats fits 160 KiB of LDS; VTC_ERR_UNSUPPORTED
+ * beyond that. */
 size_t vtc_subspace_alignment_gradient_workspace_bytes(int64_t slots,
                                                        int64_t n);
 int vtc_subspace_alignment_gradient(

@@ -143,9 +143,12 @@ __global__ __launch_bounds__(256) void fc_apply_kernel(
 // ------------------------------------------------- alignment penalty (a7)
 // One block per group.  Rows of the group are copied to LDS, the m x m table
 // of cosines is formed, then every thread owns columns of the gradient rows.
-// Per-slot gradients go to `slot_grad` (slots, n); penalty_accumulate_kernel
-// sums the slots of each atom in increasing slot order.
-constexpr int kMaxGroup = 32;
+// Per-slot gradients go to `slot_grad` (slots, n); rows_by_atom_sum_kernel
+// sums the slots of each atom in increasing slot order.  A group is bounded by
+// its LDS tile, (m n + m^2 + m) floats <= 160 KiB, and by one thread per
+// member for the norms of the un-normalised form (blockDim = 256).
+constexpr int kMaxGroup = 256;
+constexpr size_t kMaxAlignmentLds = 160 * 1024;
 
 __global__ __launch_bounds__(256) void alignment_slot_kernel(
     const float* __restrict__ D, const int32_t* __restrict__ index,
@@ -418,7 +421,7 @@ extern "C" int vtc_subspace_alignment_gradient(
   VTC_REQUIRE(s > 0 && n > 0 && groups > 0 && m > 0,
               "vtc_subspace_alignment_gradient: bad sizes");
   const size_t lds_bytes = ((size_t)m * n + (size_t)m * m + m) * sizeof(float);
-  if (m > kMaxGroup || lds_bytes > 160 * 1024) {
+  if (m > kMaxGroup || lds_bytes > kMaxAlignmentLds) {
     set_error("vtc_subspace_alignment_gradient: group of %lld atoms x %lld "
               "pixels exceeds the LDS tile", (long long)m, (long long)n);
     return VTC_ERR_UNSUPPORTED;
