@@ -31,6 +31,11 @@
  *                                                                        vtc_zca_matrices, vtc_row_transform
  *   analysis_transforms/fully_connected/invertible_linear.py:6-28
  *     (`torch.inverse(dictionary)`, training/ica.py:128-240)          -> vtc_mat_inverse (+ vtc_row_transform)
+ *   utils/image_processing.py:18-60,136-170,463-594 (filter_sd with
+ *     the Gaussian window, local_contrast_normalization,
+ *     local_luminance_subtraction, center_each_component,
+ *     center_each_sample, normalize_component_variance)               -> vtc_local_normalize, vtc_column_moments,
+ *                                                                        vtc_column_apply, vtc_row_center
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to contiguous row-major float32 unless
@@ -445,6 +450,52 @@ int vtc_row_transform(const float* x, int64_t rows, int64_t n,
 size_t vtc_mat_inverse_workspace_bytes(int64_t n);
 int vtc_mat_inverse(const float* a, int64_t n, float* a_inv, int* status,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- local normalisation and patch statistics (the preprocessing ops of
+ * utils/dataset_generation.py:22-311 that are not whitening or patching) */
+enum vtc_local_mode {
+  VTC_LOCAL_LUMINANCE = 0, /* aux = g * x, out = x - aux                     */
+  VTC_LOCAL_CONTRAST = 1   /* v = g * (x*x), v == 0 -> 1, aux = sqrt(v),
+                            * out = x / aux                                  */
+};
+enum vtc_dtype { VTC_DTYPE_F32 = 0, VTC_DTYPE_U8 = 1 };
+enum vtc_column_op {
+  VTC_COLUMN_SUBTRACT = 0,   /* out = x - v[col]                             */
+  VTC_COLUMN_DIVIDE_SQRT = 1 /* out = x / sqrt(v[col]) (no zero guard)        */
+};
+/* images, out, aux: (count, h, w, c) float32, each channel filtered on its
+ * own with the reference's Gaussian window of get_gaussian_filter_2d(sigma,
+ * (4 sigma + 1, 4 sigma + 1)) as two 1D passes accumulated in float64, 'same'
+ * size, scipy's 'symm' boundary (period-2n reflection, so any window width
+ * against any image size).  The filtered value is rounded to float32 and the
+ * mode's epilogue runs in float32 in the reference's order.  The tap count
+ * must be odd (even: VTC_ERR_INVALID_ARGUMENT); radius above 128 (sigma
+ * beyond 64): VTC_ERR_UNSUPPORTED.  Radius <= 16 runs in LDS tiles with no
+ * workspace; wider windows need vtc_local_normalize_workspace_bytes() (one
+ * float64 plane per image channel).  out and aux must not alias images or
+ * each other. */
+size_t vtc_local_normalize_workspace_bytes(int64_t count, int32_t h,
+                                           int32_t w, int32_t c,
+                                           double filter_sigma);
+int vtc_local_normalize(const float* images, float* out, float* aux,
+                        int64_t count, int32_t h, int32_t w, int32_t c,
+                        double filter_sigma, int mode, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* x (rows, cols) of dtype (float32 or uint8).  mean / var (cols float32, at
+ * least one non-NULL): the column mean and the ddof = 0 variance, summed in
+ * float64 in a fixed order (bitwise reproducible), rounded to float32. */
+size_t vtc_column_moments_workspace_bytes(int64_t rows, int64_t cols);
+int vtc_column_moments(const void* x, int dtype, int64_t rows, int64_t cols,
+                       float* mean, float* var, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* out (rows, cols) float32 = x op v[col], in float32 (uint8 x converted
+ * exactly first). */
+int vtc_column_apply(const void* x, int dtype, int64_t rows, int64_t cols,
+                     int op, const float* v, float* out, void* stream);
+/* row_means (rows float32, may be NULL) = float64 row sum / cols rounded to
+ * float32; out (rows, cols) float32 = x - row_mean in float32. */
+int vtc_row_center(const void* x, int dtype, int64_t rows, int64_t cols,
+                   float* out, float* row_means, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,10 @@ returned as float32, as the reference does with numpy.
 ZCA whitening (whiten_ZCA / unwhiten_ZCA, the reference's :338-460): float64
 covariance, Jacobi eigen-decomposition and the ZCA matrix on the device
 (vtc_hip.linalg, csrc/zca.hip), then one float32 row transform of the data.
+
+Local contrast normalisation / local luminance subtraction (the reference's
+:463-523 with filter_sd :18-60 and get_gaussian_filter_2d :136-170) and the
+component / sample statistics (:526-590): csrc/local_norm.hip.
 """
 import numpy as np
 import torch
@@ -144,3 +148,139 @@ def unwhiten_ZCA(white_flat_data, precomputed_ZCA_parameters):
   offsets = torch.full((num_components,), m, dtype=torch.float32,
                        device=x.device)
   return linalg.row_transform(x, offsets, w_inv, m)
+
+
+def gaussian_window(filter_sigma):
+  """(first coordinate, tap count) of the reference's
+  get_gaussian_filter_2d(filter_sigma, (4 sigma + 1, 4 sigma + 1)) along one
+  axis.  Host only; raises ValueError for a sigma that is not a positive
+  number or whose window has an even number of taps (an off-centre window,
+  which the separable device filter does not take)."""
+  if (isinstance(filter_sigma, (bool, np.bool_)) or
+      not isinstance(filter_sigma, (int, float, np.integer, np.floating)) or
+      not 0 < filter_sigma < 1e7):
+    raise ValueError('filter_sigma must be a positive number below 1e7, got '
+                     '%r' % (filter_sigma,))
+  window = 4 * filter_sigma + 1
+  lower = -int(np.floor(window / 2))
+  upper = int(np.floor(window / 2)) + (1 if window % 2 != 0 else 0)
+  taps = upper - lower
+  if taps % 2 == 0:
+    raise ValueError('filter_sigma %r gives a window of %d taps: only odd '
+                     'windows (centred on the pixel) are supported'
+                     % (filter_sigma, taps))
+  return lower, taps
+
+
+def _local_normalize(image, filter_sigma, mode):
+  gaussian_window(filter_sigma)
+  lib = vtc_hip.load_library()
+  image = vtc_hip.require_device_tensor(image, 'image').contiguous()
+  assert image.dim() in (3, 4), 'expected (h, w, c) or (count, h, w, c)'
+  stacked = image if image.dim() == 4 else image[None]
+  count, h, w, c = stacked.shape
+  out = torch.empty_like(stacked)
+  aux = torch.empty_like(stacked)
+  if stacked.numel():
+    ws = vtc_hip.workspace(lib.vtc_local_normalize_workspace_bytes(
+        count, h, w, c, float(filter_sigma)), image.device)
+    vtc_hip.check(lib.vtc_local_normalize(
+        vtc_hip.ptr(stacked), vtc_hip.ptr(out), vtc_hip.ptr(aux), count, h, w,
+        c, float(filter_sigma), mode, vtc_hip.ptr(ws), ws.numel(),
+        vtc_hip.current_stream(image.device)), 'vtc_local_normalize')
+  if image.dim() == 3:
+    out, aux = out[0], aux[0]
+  return out, aux
+
+
+def local_contrast_normalization(image, filter_sigma, return_normalizer=False):
+  """
+  The reference's local_contrast_normalization (image_processing.py:463-493)
+  on the device.
+
+  image : float32 tensor on a HIP device, (h, w, c) or a stack
+      (count, h, w, c) of equally sized images (an extension).
+  filter_sigma : the Gaussian's standard deviation; the window is
+      4 sigma + 1 taps wide and must have an odd tap count.
+  Returns image / sqrt(v) and, with return_normalizer, sqrt(v), where v is
+  the float32 square of the image filtered with the reference's window
+  (float64 sums, scipy's 'symm' boundary), 0 replaced by 1.
+  """
+  out, aux = _local_normalize(image, filter_sigma, vtc_hip.LOCAL_CONTRAST)
+  return (out, aux) if return_normalizer else out
+
+
+def local_luminance_subtraction(image, filter_sigma, return_subtractor=False):
+  """
+  The reference's local_luminance_subtraction (image_processing.py:496-523)
+  on the device: image - g * image with the same window and boundary as
+  local_contrast_normalization; return_subtractor adds g * image (float32).
+  """
+  out, aux = _local_normalize(image, filter_sigma, vtc_hip.LOCAL_LUMINANCE)
+  return (out, aux) if return_subtractor else out
+
+
+def _stat_input(flat_data, name):
+  """A (D, n) float32 or uint8 device tensor and its vtc_dtype code (the
+  reference accepts both, image_processing.py:544, :567, :590)."""
+  if torch.is_tensor(flat_data) and flat_data.dtype == torch.uint8:
+    x = vtc_hip.require_device_tensor(flat_data, name, torch.uint8)
+    code = vtc_hip.DTYPE_U8
+  else:
+    x = vtc_hip.require_device_tensor(flat_data, name)
+    code = vtc_hip.DTYPE_F32
+  assert x.dim() == 2 and x.shape[0] > 0 and x.shape[1] > 0, (
+      '%s must be a non-empty (D, n)' % name)
+  return x.contiguous(), code
+
+
+def _column_moments(x, code, want_var):
+  lib = vtc_hip.load_library()
+  rows, cols = x.shape
+  mean = torch.empty(cols, dtype=torch.float32, device=x.device)
+  var = torch.empty_like(mean) if want_var else None
+  ws = vtc_hip.workspace(lib.vtc_column_moments_workspace_bytes(rows, cols),
+                         x.device)
+  vtc_hip.check(lib.vtc_column_moments(
+      vtc_hip.ptr(x), code, rows, cols, vtc_hip.ptr(mean), vtc_hip.ptr(var),
+      vtc_hip.ptr(ws), ws.numel(), vtc_hip.current_stream(x.device)),
+      'vtc_column_moments')
+  return mean, var
+
+
+def _column_apply(x, code, op, v):
+  out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+  vtc_hip.check(vtc_hip.load_library().vtc_column_apply(
+      vtc_hip.ptr(x), code, x.shape[0], x.shape[1], op, vtc_hip.ptr(v),
+      vtc_hip.ptr(out), vtc_hip.current_stream(x.device)), 'vtc_column_apply')
+  return out
+
+
+def center_each_component(flat_data):
+  """The reference's center_each_component (image_processing.py:527-547):
+  flat_data (D, n) float32 or uint8 on the device -> (flat_data - means as
+  float32, means (n,) float32).  Means are float64 sums rounded to float32."""
+  x, code = _stat_input(flat_data, 'flat_data')
+  mean, _ = _column_moments(x, code, want_var=False)
+  return _column_apply(x, code, vtc_hip.COLUMN_SUBTRACT, mean), mean
+
+
+def normalize_component_variance(flat_data):
+  """The reference's normalize_component_variance (image_processing.py:
+  573-594): (flat_data / sqrt(variances), variances (n,) float32), ddof = 0;
+  a zero-variance column is not guarded, as in the reference."""
+  x, code = _stat_input(flat_data, 'flat_data')
+  _, var = _column_moments(x, code, want_var=True)
+  return _column_apply(x, code, vtc_hip.COLUMN_DIVIDE_SQRT, var), var
+
+
+def center_each_sample(flat_data):
+  """The reference's center_each_sample (image_processing.py:550-570):
+  (flat_data - row means, row means (D,) float32)."""
+  x, code = _stat_input(flat_data, 'flat_data')
+  out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+  means = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+  vtc_hip.check(vtc_hip.load_library().vtc_row_center(
+      vtc_hip.ptr(x), code, x.shape[0], x.shape[1], vtc_hip.ptr(out),
+      vtc_hip.ptr(means), vtc_hip.current_stream(x.device)), 'vtc_row_center')
+  return out, means

@@ -24,6 +24,9 @@ ISTA, FISTA = 0, 1
 SOFT, SOFT_NONNEG, HARD, HARD_NONNEG = range(4)
 F32, BF16X3, BF16, F16X3 = range(4)
 PRECISIONS = {'f32': F32, 'bf16x3': BF16X3, 'bf16': BF16, 'f16x3': F16X3}
+LOCAL_LUMINANCE, LOCAL_CONTRAST = range(2)
+DTYPE_F32, DTYPE_U8 = range(2)
+COLUMN_SUBTRACT, COLUMN_DIVIDE_SQRT = range(2)
 ABI_VERSION = 4   # VTC_ABI_VERSION of include/vtc_hip.h this binding matches
 
 _lib = None
@@ -136,6 +139,15 @@ SIGNATURES = {
     'vtc_row_transform': (_i32, [_vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp]),
     'vtc_mat_inverse_workspace_bytes': (_sz, [_i64]),
     'vtc_mat_inverse': (_i32, [_vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    'vtc_local_normalize_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32,
+                                                   ctypes.c_double]),
+    'vtc_local_normalize': (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32,
+                                   ctypes.c_double, _i32, _vp, _sz, _vp]),
+    'vtc_column_moments_workspace_bytes': (_sz, [_i64, _i64]),
+    'vtc_column_moments': (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _sz,
+                                  _vp]),
+    'vtc_column_apply': (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'vtc_row_center': (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp]),
 }
 
 
