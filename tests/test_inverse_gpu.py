@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import fences
 import ica_data
 
 pytestmark = pytest.mark.gpu
@@ -114,12 +115,16 @@ def test_canary_bytes_around_the_output_are_untouched(device, n):
   buf = torch.full((n * n + 2 * pad,), float(canary), dtype=torch.float32,
                    device=device)
   status = torch.empty(2, dtype=torch.int32, device=device)
-  ws = vtc_hip.workspace(lib.vtc_mat_inverse_workspace_bytes(n), device)
+  # the workspace at exactly the queried size, 0xFF-filled, between guards
+  ws, ws_fence = fences.fenced_workspace(
+      lib.vtc_mat_inverse_workspace_bytes(n), device)
+  assert ws.numel() == lib.vtc_mat_inverse_workspace_bytes(n)
   out = buf[pad:pad + n * n]
   vtc_hip.check(lib.vtc_mat_inverse(
       vtc_hip.ptr(a), n, ctypes.c_void_p(out.data_ptr()), vtc_hip.ptr(status),
       vtc_hip.ptr(ws), ws.numel(), vtc_hip.current_stream(device)),
       'vtc_mat_inverse')
+  ws_fence.assert_intact('vtc_mat_inverse workspace, n = %d' % n)
   host = buf.cpu().numpy()
   assert np.all(host[:pad] == canary) and np.all(host[pad + n * n:] == canary)
   assert status.tolist() == [1, -1]
