@@ -41,18 +41,40 @@ static inline size_t align_up(size_t v, size_t a) {
   return (v + a - 1) / a * a;
 }
 
-// Carves 256-byte aligned pieces out of the caller's workspace.
+// Carves 256-byte aligned pieces out of the caller's workspace.  Built on a
+// null base it only measures: take<>() returns null and `used` still advances.
+// Every route states its scratch once, as a layout type whose constructor does
+// the take<>() calls; the route's byte count is that constructor run on a
+// measuring Carver (measured_bytes), the work runs it on the caller's pointer.
 struct Carver {
   char* base;
   size_t used;
   explicit Carver(void* p) : base(static_cast<char*>(p)), used(0) {}
   template <class T>
   T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(base + used);
+    T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
     used += align_up(count * sizeof(T), 256);
     return p;
   }
+  // a workspace that is one array and publishes its size without padding
+  template <class T>
+  T* take_unpadded(size_t count) {
+    T* p = take<T>(0);
+    used += count * sizeof(T);
+    return p;
+  }
 };
+
+template <class Layout, class... Shape>
+static inline size_t measured_bytes(const Shape&... shape) {
+  Carver measure(nullptr);
+  (void)Layout(measure, shape...);
+  return measure.used;
+}
+
+// Compute units of the current device, cached per device ordinal; 256 (the
+// MI355X count) when no device answers.  runtime.cpp
+int compute_units();
 
 // Function attributes (dynamic LDS above 64 KiB) are per device and a process
 // may drive several: true the first time the calling site runs on the current

@@ -447,28 +447,67 @@ __global__ __launch_bounds__(1024) void conv_apply_kernel(
   }
 }
 
-static size_t conv_x3_image_bytes(const ConvGeo& g) {
-  CxPlan p;
-  return cx_plan(g, &p) ? cx_image_bytes(p) + cx_fused_bytes(p) : 0;
-}
-
 // f16x3 scale state (x3_scale.h, CxScales): {sigma_D, 1 / sigma_D} and, per
 // image, two words each for max |R| and max |Y|
 static size_t cx_state_words(const ConvGeo& g) {
   return 64 + 4 * (size_t)g.b;
 }
 
+// Scratch of convolutional inference.  xp: the split-mode plan when that route
+// runs (null otherwise), fused: its fused iteration kernel too, patch: the
+// strided exact-f32 patch contraction.
+struct ConvIstaLayout {
+  float* Ybuf;
+  float* Yalt;            // out-of-place targets of the
+  float* Calt;            // two-kernel routes (ProxParams)
+  float* residual;        // residual, or up to 8 partial sums of it
+  float* Kt;
+  unsigned* state;        // f16x3 scales (conv_x3.h, CxScales)
+  uint16_t* syn_image = nullptr;
+  uint16_t* ana_image = nullptr;
+  uint16_t* synp_image = nullptr;   // fused iteration kernel (conv_x3.h)
+  float* partial = nullptr;
+  float* Cfrag1 = nullptr;          // the last two code iterates of that
+  float* Cfrag0 = nullptr;          // kernel, fragment order (CxMaps)
+  float* patches = nullptr;         // im2col P and the per-position
+  float* contributions = nullptr;   // contributions Q (conv_patch.h)
+  double* delta_sum;
+  ConvIstaLayout(Carver& ws, const ConvGeo& g, const CxPlan* xp, bool fused,
+                 bool patch) {
+    const size_t code_elems = (size_t)g.b * g.s * g.ch * g.cw;
+    const size_t ctaps = (size_t)g.c * g.kh * g.kw;
+    Ybuf = ws.take<float>(code_elems);
+    Yalt = ws.take<float>(code_elems);
+    Calt = ws.take<float>(code_elems);
+    residual = ws.take<float>(8 * (size_t)g.b * g.c * g.H * g.W);
+    Kt = ws.take<float>((size_t)g.s * ctaps);
+    state = ws.take<unsigned>(cx_state_words(g));
+    if (xp) {
+      syn_image = ws.take<uint16_t>(xp->syn_image_bytes / 2);
+      ana_image = ws.take<uint16_t>(xp->ana_image_bytes / 2);
+    }
+    if (xp && fused) {
+      synp_image = ws.take<uint16_t>(xp->synp_image_bytes / 2);
+      partial = ws.take<float>(xp->partial_bytes / sizeof(float));
+      Cfrag1 = ws.take<float>(xp->padded_bytes / sizeof(float));
+      Cfrag0 = ws.take<float>(xp->padded_bytes / sizeof(float));
+    }
+    if (patch) {
+      const size_t elems = (size_t)g.b * g.ch * g.cw * ctaps;
+      patches = ws.take<float>(elems);
+      contributions = ws.take<float>(elems);
+    }
+    delta_sum = ws.take<double>(1);
+  }
+};
+
+// One size for every precision: the pieces of all routes the geometry has.
 static size_t conv_inference_ws(const ConvGeo& g) {
-  const size_t code_elems = (size_t)g.b * g.s * g.ch * g.cw;
-  const size_t img_elems = (size_t)g.b * g.c * g.H * g.W;
-  return 3 * align_up(code_elems * sizeof(float), 256) +      // Y, Y', C'
-         align_up(8 * img_elems * sizeof(float), 256) +       // residual or
-                                                              // <= 8 partials
-         align_up((size_t)g.s * g.c * g.kh * g.kw * 4, 256) + // Kt
-         conv_x3_image_bytes(g) +                             // bf16x3 operands
-         patch_workspace_bytes(g) +                           // im2col, Q
-         align_up(cx_state_words(g) * sizeof(unsigned), 256) + // f16x3 scales
-         256;
+  CxPlan xp;
+  const bool x3 = cx_plan(g, &xp);
+  return measured_bytes<ConvIstaLayout>(g, x3 ? &xp : nullptr,
+                                        x3 && xp.fused_lds != 0,
+                                        patch_geometry(g));
 }
 
 static int launch_synthesis(const float* codes, const float* D,
@@ -492,6 +531,46 @@ static int launch_synthesis(const float* codes, const float* D,
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }
+
+// Blocks of the f32 gradient kernel (conv_grad_kernel), one slab each
+static int conv_grad_blocks(const ConvGeo& g) {
+  const AnaPlan ap = plan_analysis(g);
+  return grad_blocks(g.b * ceil_div(g.ch, ap.tp) * ceil_div(g.cw, ap.tq));
+}
+
+// Slabs a route of the dictionary gradient is given.  f32: one per block, or
+// one per image where the small patch contraction runs; split modes (x3):
+// what the matrix-core kernel writes, and never fewer than the f32 route.
+static size_t conv_grad_slab_count(const ConvGeo& g, bool x3) {
+  const size_t blocks = (size_t)conv_grad_blocks(g);
+  if (x3)
+    return (size_t)cx_grad_blocks(g) > blocks ? (size_t)cx_grad_blocks(g)
+                                              : blocks;
+  return patch_gradient_small(g) && blocks < (size_t)g.b ? (size_t)g.b
+                                                          : blocks;
+}
+
+// Scratch of the dictionary gradient.  xp: the split-mode plan when that route
+// runs (null otherwise); patch: strided geometries, whose residual comes from
+// the patch contraction (conv_patch.h) and needs its contributions Q.
+struct ConvGradLayout {
+  float* residual;
+  float* slabs;
+  uint16_t* syn_image = nullptr;
+  uint16_t* ana_image = nullptr;
+  float* Q = nullptr;
+  ConvGradLayout(Carver& ws, const ConvGeo& g, size_t slab_count,
+                 const CxPlan* xp, bool patch) {
+    const size_t ctaps = (size_t)g.c * g.kh * g.kw;
+    residual = ws.take<float>((size_t)g.b * g.c * g.H * g.W);
+    slabs = ws.take<float>(slab_count * g.s * ctaps);
+    if (xp) {
+      syn_image = ws.take<uint16_t>(xp->syn_image_bytes / 2);
+      ana_image = ws.take<uint16_t>(xp->ana_image_bytes / 2);
+    }
+    if (patch) Q = ws.take<float>((size_t)g.b * g.ch * g.cw * ctaps);
+  }
+};
 
 }  // namespace vtc
 
@@ -557,22 +636,19 @@ extern "C" int vtc_conv_ista_fista(
   }
   hipStream_t st = as_stream(stream);
   const size_t code_elems = (size_t)g.b * g.s * g.ch * g.cw;
-  const size_t img_elems = (size_t)g.b * g.c * g.H * g.W;
   const int ctaps = g.c * g.kh * g.kw;
+  // fused iteration kernel (kernels up to 11x11, more than 32 of them)
+  static const bool no_fused = getenv("VTC_CONV_NO_FUSED") != nullptr;
+  const bool patch_path = !x3 && patch_geometry(g);
   Carver ws(workspace);
-  float* Ybuf = ws.take<float>(code_elems);
-  float* Yalt = ws.take<float>(code_elems);   // out-of-place targets of the
-  float* Calt = ws.take<float>(code_elems);   // two-kernel routes (ProxParams)
-  float* residual = ws.take<float>(8 * img_elems);
-  float* Kt = ws.take<float>((size_t)g.s * ctaps);
-  uint16_t* syn_image = nullptr;
-  uint16_t* ana_image = nullptr;
-  uint16_t* synp_image = nullptr;   // fused iteration kernel (conv_x3.h)
-  float* partial = nullptr;
-  float* Cfrag1 = nullptr;          // the last two code iterates of that
-  float* Cfrag0 = nullptr;          // kernel, fragment order (CxMaps)
+  const ConvIstaLayout L(ws, g, x3 ? &xp : nullptr,
+                         x3 && xp.fused_lds != 0 && !no_fused, patch_path);
+  float* residual = L.residual;
+  uint16_t* synp_image = L.synp_image;
+  float* Cfrag1 = L.Cfrag1;
+  float* Cfrag0 = L.Cfrag0;
   // f16x3: power-of-two scales of the operands (conv_x3.h, CxScales)
-  unsigned* state = ws.take<unsigned>(cx_state_words(g));
+  unsigned* state = L.state;
   float* dscale = f16 ? reinterpret_cast<float*>(state) : nullptr;
   unsigned* r_slot[2] = {state + 64, state + 64 + g.b};
   unsigned* y_slot[2] = {state + 64 + 2 * g.b, state + 64 + 3 * g.b};
@@ -591,16 +667,8 @@ extern "C" int vtc_conv_ista_fista(
     }
   }
   if (x3) {
-    syn_image = ws.take<uint16_t>(xp.syn_image_bytes / 2);
-    ana_image = ws.take<uint16_t>(xp.ana_image_bytes / 2);
-    rc = cx_pack(dictionary, g, xp, syn_image, ana_image, dscale, st);
-    // fused iteration kernel (kernels up to 11x11, more than 32 of them)
-    static const bool no_fused = getenv("VTC_CONV_NO_FUSED") != nullptr;
-    if (rc == VTC_OK && xp.fused_lds != 0 && !no_fused) {
-      synp_image = ws.take<uint16_t>(xp.synp_image_bytes / 2);
-      partial = ws.take<float>(xp.partial_bytes / sizeof(float));
-      Cfrag1 = ws.take<float>(xp.padded_bytes / sizeof(float));
-      Cfrag0 = ws.take<float>(xp.padded_bytes / sizeof(float));
+    rc = cx_pack(dictionary, g, xp, L.syn_image, L.ana_image, dscale, st);
+    if (rc == VTC_OK && synp_image) {
       if (f16)
         hipLaunchKernelGGL(conv_x3_pack_synp_kernel<true>, dim3(256),
                            dim3(256), 0, st, dictionary, synp_image, g.s, xp.k,
@@ -613,17 +681,8 @@ extern "C" int vtc_conv_ista_fista(
     }
     if (rc != VTC_OK) return rc;
   }
-  const bool patch_path = !x3 && patch_geometry(g);
-  float* patches = nullptr;
-  float* contributions = nullptr;
-  if (patch_path) {
-    const size_t elems = (size_t)g.b * g.ch * g.cw * ctaps;
-    patches = ws.take<float>(elems);
-    contributions = ws.take<float>(elems);
-  }
-  double* delta_sum = ws.take<double>(1);
   const bool fista = (variant == VTC_FISTA);
-  float* Y = fista ? Ybuf : codes;
+  float* Y = fista ? L.Ybuf : codes;
   const size_t code_bytes = code_elems * sizeof(float);
   if (initial_codes) {
     VTC_HIP_CHECK(hipMemcpyAsync(codes, initial_codes, code_bytes,
@@ -637,7 +696,7 @@ extern "C" int vtc_conv_ista_fista(
   }
   hipLaunchKernelGGL(transpose_kernels_kernel,
                      dim3((unsigned)ceil_div((int64_t)g.s * ctaps, 256)),
-                     dim3(256), 0, st, dictionary, Kt, g.s, ctaps);
+                     dim3(256), 0, st, dictionary, L.Kt, g.s, ctaps);
   VTC_LAUNCH_CHECK();
 
   const AnaPlan ap = plan_analysis(g);
@@ -658,15 +717,15 @@ extern "C" int vtc_conv_ista_fista(
   int done = 0;
   // two-kernel routes: (Y, C) -> (y_out, c_out), buffers swapped per iteration
   float* Cin = codes;
-  float* Cout = Calt;
-  float* Yout = Yalt;
+  float* Cout = L.Calt;
+  float* Yout = L.Yalt;
   const float* frag_latest = nullptr;   // fused path: newest codes (fragments)
   for (int k = 0; k < num_iters; ++k) {
     if (eps >= 0.f)
-      VTC_HIP_CHECK(hipMemsetAsync(delta_sum, 0, sizeof(double), st));
+      VTC_HIP_CHECK(hipMemsetAsync(L.delta_sum, 0, sizeof(double), st));
     if (!fista) Y = Cin;                        // ISTA iterates on the codes
     ProxParams pp{eta, cutoff, fista ? betas[k] : 0.f, threshold,
-                  fista ? 1 : 0, eps >= 0.f ? delta_sum : nullptr,
+                  fista ? 1 : 0, eps >= 0.f ? L.delta_sum : nullptr,
                   Yout, Cout};
     if (x3 && synp_image) {
       // synthesis fused into the analysis epilogue: the residual of the first
@@ -678,7 +737,7 @@ extern "C" int vtc_conv_ista_fista(
       if (k == 0) {
         CxScales first{dscale, nullptr, r_slot[0], nullptr, y_slot[0], nullptr,
                        nullptr, images};
-        rc = cx_launch_synth(codes, syn_image, images_padded, residual, g, xp,
+        rc = cx_launch_synth(codes, L.syn_image, images_padded, residual, g, xp,
                              first, st);
         if (rc != VTC_OK) return rc;
         VTC_HIP_CHECK(hipMemsetAsync(Cfrag1, 0, xp.padded_bytes, st));
@@ -705,7 +764,7 @@ extern "C" int vtc_conv_ista_fista(
       // residual kernel behind it leaves max |R_(k+1)|
       CxScales sc{dscale, r_slot[k & 1], r_slot[(k + 1) & 1],
                   r_slot[(k + 1) & 1], nullptr, nullptr, nullptr, images};
-      rc = cx_launch_fused(residual, ana_image, synp_image, maps, partial,
+      rc = cx_launch_fused(residual, L.ana_image, synp_image, maps, L.partial,
                            images_padded, residual, g, xp, pp,
                            k + 1 < num_iters, sc, st);
       if (rc != VTC_OK) return rc;
@@ -716,20 +775,20 @@ extern "C" int vtc_conv_ista_fista(
       // the slot of max |R_(k+1)|
       CxScales syn_sc{dscale, nullptr, r_slot[k & 1], nullptr, y_slot[k & 1],
                       nullptr, y_slot[(k + 1) & 1], images};
-      rc = cx_launch_synth(Y, syn_image, images_padded, residual, g, xp,
+      rc = cx_launch_synth(Y, L.syn_image, images_padded, residual, g, xp,
                            syn_sc, st);
       if (rc != VTC_OK) return rc;
       CxScales ana_sc{dscale, r_slot[k & 1], nullptr, r_slot[(k + 1) & 1],
                       nullptr, y_slot[(k + 1) & 1], nullptr, images};
-      rc = cx_launch_analysis(residual, ana_image, Y, Cin, g, xp, pp, ana_sc,
+      rc = cx_launch_analysis(residual, L.ana_image, Y, Cin, g, xp, pp, ana_sc,
                               st);
       if (rc != VTC_OK) return rc;
     } else if (patch_path) {
       // strides > 1: both convolutions as exact-f32 patch contractions
       rc = patch_synthesis(Y, dictionary, images_padded, residual,
-                           contributions, g, st);
+                           L.contributions, g, st);
       if (rc != VTC_OK) return rc;
-      rc = patch_analysis(residual, dictionary, Y, Cin, patches, g, pp, st);
+      rc = patch_analysis(residual, dictionary, Y, Cin, L.patches, g, pp, st);
       if (rc != VTC_OK) return rc;
     } else if (unit_path) {
       // stride-1 square kernels: scalar-tap kernels, the kernel sum of the
@@ -745,7 +804,7 @@ extern "C" int vtc_conv_ista_fista(
       if (rc != VTC_OK) return rc;
       hipLaunchKernelGGL(conv_analysis_prox_kernel,
                          dim3((unsigned)(tiles_p * tiles_q), (unsigned)g.b),
-                         dim3(256), ap.lds_bytes, st, residual, Kt, Y, Cin,
+                         dim3(256), ap.lds_bytes, st, residual, L.Kt, Y, Cin,
                          g, ap.tp, ap.tq, ap.wy, ap.wx, tiles_q, pp);
       VTC_LAUNCH_CHECK();
     }
@@ -757,7 +816,7 @@ extern "C" int vtc_conv_ista_fista(
     done = k + 1;
     if (eps >= 0.f) {
       double total = 0.0;
-      VTC_HIP_CHECK(hipMemcpyAsync(&total, delta_sum, sizeof(double),
+      VTC_HIP_CHECK(hipMemcpyAsync(&total, L.delta_sum, sizeof(double),
                                    hipMemcpyDeviceToHost, st));
       VTC_HIP_CHECK(hipStreamSynchronize(st));
       const float mean = (float)(total / (double)code_elems);
@@ -798,25 +857,15 @@ extern "C" size_t vtc_conv_dict_gradient_workspace_bytes(
     const vtc_conv_geometry* geom) {
   ConvGeo g;
   if (make_geo(geom, &g) != VTC_OK || g.b == 0) return 256;
-  const AnaPlan ap = plan_analysis(g);
-  const int64_t tiles =
-      g.b * ceil_div(g.ch, ap.tp) * ceil_div(g.cw, ap.tq);
-  size_t slab_count = (size_t)grad_blocks(tiles);
-  if (patch_gradient_small(g) && slab_count < (size_t)g.b) slab_count = g.b;
-  size_t extra = 0;
+  // one size for every precision: the larger slab count and the pieces of
+  // both routes
+  size_t slab_count = conv_grad_slab_count(g, false);
   CxPlan xp;
-  if (cx_plan(g, &xp)) {                            // bf16x3 route
-    if ((size_t)cx_grad_blocks(g) > slab_count) slab_count = cx_grad_blocks(g);
-    extra = cx_image_bytes(xp);
-  }
-  // strided geometries: the residual comes from the patch contraction
-  // (conv_patch.h), which needs its per-position contributions Q
-  if (patch_geometry(g))
-    extra += align_up((size_t)g.b * g.ch * g.cw * g.c * g.kh * g.kw *
-                          sizeof(float), 256);
-  return align_up((size_t)g.b * g.c * g.H * g.W * sizeof(float), 256) +
-         align_up(slab_count * g.s * g.c * g.kh * g.kw * sizeof(float), 256) +
-         extra;
+  const bool x3 = cx_plan(g, &xp);
+  if (x3 && conv_grad_slab_count(g, true) > slab_count)
+    slab_count = conv_grad_slab_count(g, true);
+  return measured_bytes<ConvGradLayout>(g, slab_count, x3 ? &xp : nullptr,
+                                        patch_geometry(g));
 }
 
 extern "C" int vtc_conv_dict_gradient(const float* images_padded,
@@ -852,19 +901,19 @@ extern "C" int vtc_conv_dict_gradient(const float* images_padded,
   const int tiles_q = (int)ceil_div(g.cw, ap.tq);
   const int64_t tiles_per_image = ceil_div(g.ch, ap.tp) * tiles_q;
   const int64_t total_tiles = g.b * tiles_per_image;
-  const int blocks = grad_blocks(total_tiles);
+  const int blocks = conv_grad_blocks(g);
   const int64_t dict_elems = (int64_t)g.s * g.c * g.kh * g.kw;
   Carver ws(workspace);
-  float* residual = ws.take<float>((size_t)g.b * g.c * g.H * g.W);
+  const ConvGradLayout L(ws, g, conv_grad_slab_count(g, x3),
+                         x3 ? &xp : nullptr, !x3 && patch_geometry(g));
+  float* residual = L.residual;
   if (x3) {
     // residual and gradient on the matrix cores (conv_x3.h); the slab sum and
     // everything after it are the same as on the f32 route
     const int xblocks = cx_grad_blocks(g);
-    float* xslabs = ws.take<float>((size_t)(xblocks > blocks ? xblocks
-                                                              : blocks) *
-                                   dict_elems);
-    uint16_t* syn_image = ws.take<uint16_t>(xp.syn_image_bytes / 2);
-    uint16_t* ana_image = ws.take<uint16_t>(xp.ana_image_bytes / 2);
+    float* xslabs = L.slabs;
+    uint16_t* syn_image = L.syn_image;
+    uint16_t* ana_image = L.ana_image;
     // (the gradient stays on the bf16 split: a single product, no iteration
     // to amplify its 2^-17, and its tests hold 5e-6 on the updated kernels)
     const CxScales none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -878,14 +927,12 @@ extern "C" int vtc_conv_dict_gradient(const float* images_padded,
     if (rc != VTC_OK) return rc;
     return launch_slab_reduce(xslabs, xblocks, dict_elems, grad_sum, st);
   }
-  float* slabs = ws.take<float>(
-      (size_t)(patch_gradient_small(g) && blocks < g.b ? g.b : blocks) *
-      dict_elems);
-  if (patch_geometry(g)) {
+  float* slabs = L.slabs;
+  if (L.Q) {
     // (the direct synthesis kernel spends ~30 integer instructions per FMA on
     // strided geometries: 135 us against 19 at the reference's example size)
-    float* Q = ws.take<float>((size_t)g.b * g.ch * g.cw * g.c * g.kh * g.kw);
-    rc = patch_synthesis(codes, dictionary, images_padded, residual, Q, g, st);
+    rc = patch_synthesis(codes, dictionary, images_padded, residual, L.Q, g,
+                         st);
   } else {
     rc = launch_synthesis(codes, dictionary, images_padded, residual, g, st);
   }

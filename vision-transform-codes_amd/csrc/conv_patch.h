@@ -30,12 +30,6 @@ static bool patch_geometry(const ConvGeo& g) {
          (int64_t)g.b * g.ch * g.cw < ((int64_t)1 << 31);  // 32-bit positions
 }
 
-static size_t patch_workspace_bytes(const ConvGeo& g) {
-  if (!patch_geometry(g)) return 0;
-  const size_t elems = (size_t)g.b * g.ch * g.cw * g.c * g.kh * g.kw;
-  return 2 * align_up(elems * sizeof(float), 256);   // P and Q
-}
-
 // P[pos][t] = R[img][c][p*sv + dy][q*sh + dx]
 __global__ void conv_im2col_kernel(const float* __restrict__ R,
                                    float* __restrict__ P, ConvGeo g) {

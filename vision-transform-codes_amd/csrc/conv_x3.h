@@ -1630,20 +1630,6 @@ struct CxPlan {
   size_t padded_bytes;   // one fragment-order set of code maps
 };
 
-static int cx_compute_units() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
-                              dev) == hipSuccess && n > 0)
-      cus = n;
-    else
-      cus = 256;
-  }
-  return cus;
-}
-
 // Code rows per wave of the synthesis kernel.  One block per CU is resident
 // (the operand planes fill most of the LDS), a block's work grows with the
 // rows, its halo overhead shrinks with them: take the count that minimises
@@ -1652,7 +1638,7 @@ static int cx_compute_units() {
 // 2 rounds; measured 0.070 -> 0.063 ms per image-iteration.)
 static int cx_pick_rows(const ConvGeo& g, int k, int tw, int pw,
                         size_t image_bytes) {
-  const int cus = cx_compute_units();
+  const int cus = compute_units();
   const int64_t tiles_x = ceil_div(g.W, tw);
   int best = 0;
   int64_t best_cost = 0;
@@ -1709,7 +1695,7 @@ static void cx_fill_plan(const ConvGeo& g, CxPlan* p) {
   {
     const int64_t blocks8 = ceil_div(g.cw, kCxStrip) *
                             ceil_div(g.ch, kCxAnaMaxRows) * p->chunks * g.b;
-    p->ana_rows = blocks8 < (int64_t)16 * cx_compute_units() ? 4 : 8;
+    p->ana_rows = blocks8 < (int64_t)16 * compute_units() ? 4 : 8;
   }
   {
     const size_t planes = (size_t)2 * K * p->AC * 16 * 2;
@@ -1773,16 +1759,6 @@ static bool cx_plan(const ConvGeo& g, CxPlan* p) {
          g.b <= 65535 && code_bytes < (int64_t)0x7fffffff;
 }
 
-static size_t cx_image_bytes(const CxPlan& p) {
-  return align_up(p.syn_image_bytes, 256) + align_up(p.ana_image_bytes, 256);
-}
-
-// extra workspace of the fused iteration kernel
-static size_t cx_fused_bytes(const CxPlan& p) {
-  return align_up(p.synp_image_bytes, 256) + align_up(p.partial_bytes, 256) +
-         2 * align_up(p.padded_bytes, 256);
-}
-
 template <int K, bool RAGGED, bool F16>
 static int cx_launch_fused_k(const float* R, const uint16_t* ana,
                              const uint16_t* synp, const CxMaps& maps,
@@ -1807,7 +1783,7 @@ static int cx_launch_fused_k(const float* R, const uint16_t* ana,
   // persistent blocks, one per CU: the same number for every (XCD, chunk)
   const int64_t bands = (int64_t)g.b * tiles_u;
   const int64_t items_per_xcd = ceil_div(bands, 8) * tiles_v;
-  int64_t nper = cx_compute_units() / (8 * p.chunks);
+  int64_t nper = compute_units() / (8 * p.chunks);
   if (nper < 1) nper = 1;
   if (nper > items_per_xcd) nper = items_per_xcd;
   const int64_t blocks = 8 * nper * p.chunks;
@@ -2005,7 +1981,7 @@ static int cx_launch_analysis(const float* R, const uint16_t* ana, float* Y,
 static int cx_grad_blocks(const ConvGeo& g) {
   const int64_t items = ceil_div(g.cw, kCxStrip) *
                         ceil_div(g.ch, kCxGradRows) * g.b;
-  const int64_t want = (int64_t)4 * cx_compute_units();
+  const int64_t want = (int64_t)4 * compute_units();
   return (int)(items < want ? items : want);
 }
 

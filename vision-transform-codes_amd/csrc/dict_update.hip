@@ -280,6 +280,52 @@ static int energy_chunk_rows(int64_t b) {
   return (int)rows;
 }
 
+
+// ---- workspace layouts (one per entry point: its query measures it, its call
+// carves it)
+struct FcGradLayout {
+  float* E;       // residual (b, n)
+  float* slabs;   // split-K slabs of C^T E
+  FcGradLayout(Carver& ws, int64_t b, int64_t n, int64_t s) {
+    E = ws.take<float>((size_t)b * n);
+    slabs = ws.take<float>((size_t)gradient_slices(b, n, s) * s * n);
+  }
+};
+
+struct SlotGradLayout {
+  float* slot_grad;   // (slots, n), at least one row
+  SlotGradLayout(Carver& ws, int64_t slots, int64_t n) {
+    slot_grad = ws.take<float>((size_t)(slots > 0 ? slots : 1) * n);
+  }
+};
+
+struct EnergyLayout {
+  int64_t chunks;   // partial sums per atom: one per image of code maps, one
+  float* partial;   // per chunk of rows of (b, s) codes
+  EnergyLayout(Carver& ws, int64_t b, int64_t s, int64_t positions) {
+    chunks = positions > 1 ? b : ceil_div(b, energy_chunk_rows(b));
+    partial = ws.take<float>((size_t)chunks * s);
+  }
+};
+
+struct IcaMomentLayout {
+  float* S;       // sign(codes)
+  float* slabs;   // split-K slabs of C^T sign(C)
+  IcaMomentLayout(Carver& ws, int64_t b, int64_t s) {
+    S = ws.take<float>((size_t)b * s);
+    slabs = ws.take<float>((size_t)gradient_slices(b, s, s) * s * s);
+  }
+};
+
+struct IcaApplyLayout {
+  float* T;   // M / b - I
+  float* U;   // T D
+  IcaApplyLayout(Carver& ws, int64_t s, int64_t n) {
+    T = ws.take<float>((size_t)s * s);
+    U = ws.take<float>((size_t)s * n);
+  }
+};
+
 }  // namespace vtc
 
 using namespace vtc;
@@ -304,10 +350,7 @@ extern "C" int vtc_gram(const float* a, int64_t rows, int64_t cols,
 extern "C" size_t vtc_fc_dict_gradient_workspace_bytes(int64_t b, int64_t n,
                                                        int64_t s) {
   if (b <= 0 || n <= 0 || s <= 0) return 256;
-  size_t bytes = align_up((size_t)b * n * sizeof(float), 256);  // residual
-  bytes += align_up((size_t)gradient_slices(b, n, s) * s * n * sizeof(float),
-                    256);
-  return bytes;
+  return measured_bytes<FcGradLayout>(b, n, s);
 }
 
 extern "C" int vtc_fc_dict_gradient(const float* images,
@@ -326,11 +369,10 @@ extern "C" int vtc_fc_dict_gradient(const float* images,
   }
   hipStream_t st = as_stream(stream);
   Carver ws(workspace);
-  float* E = ws.take<float>((size_t)b * n);
+  const FcGradLayout L(ws, b, n, s);
   const int slices = gradient_slices(b, n, s);
-  float* slabs = ws.take<float>((size_t)slices * s * n);
   // E = C D - X
-  EpiMinus e1{E, images, n, n};
+  EpiMinus e1{L.E, images, n, n};
   int rc = launch_gemm_f32<true, false>(codes, s, dictionary, n, b, n, s, 1,
                                         e1, st);
   if (rc != VTC_OK) return rc;
@@ -339,14 +381,14 @@ extern "C" int vtc_fc_dict_gradient(const float* images,
   // straight into grad_sum -- no slabs, no reduction pass.
   if (b <= 512 && gemm_prefers_small(s, n)) {
     EpiStore direct{grad_sum, n};
-    return launch_gemm_f32<false, false>(codes, s, E, n, s, n, b, 1, direct,
+    return launch_gemm_f32<false, false>(codes, s, L.E, n, s, n, b, 1, direct,
                                          st);
   }
   // otherwise K = b split into slabs
-  EpiSlab e2{slabs, s * n, n};
-  rc = launch_gemm_f32<false, false>(codes, s, E, n, s, n, b, slices, e2, st);
+  EpiSlab e2{L.slabs, s * n, n};
+  rc = launch_gemm_f32<false, false>(codes, s, L.E, n, s, n, b, slices, e2, st);
   if (rc != VTC_OK) return rc;
-  return launch_slab_reduce(slabs, slices, s * n, grad_sum, st);
+  return launch_slab_reduce(L.slabs, slices, s * n, grad_sum, st);
 }
 
 // ---------------------------------------------- ICA natural gradient (f4)
@@ -408,7 +450,7 @@ extern "C" int vtc_fc_residual(const float* images, const float* dictionary,
 
 extern "C" size_t vtc_subspace_alignment_gradient_workspace_bytes(
     int64_t slots, int64_t n) {
-  return align_up((size_t)(slots > 0 ? slots : 1) * n * sizeof(float), 256);
+  return measured_bytes<SlotGradLayout>(slots, n);
 }
 
 extern "C" int vtc_subspace_alignment_gradient(
@@ -432,7 +474,8 @@ extern "C" int vtc_subspace_alignment_gradient(
     return VTC_ERR_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
-  float* slot_grad = static_cast<float*>(workspace);
+  Carver ws(workspace);
+  float* slot_grad = SlotGradLayout(ws, groups * m, n).slot_grad;
   VTC_HIP_CHECK(hipMemsetAsync(slot_grad, 0,
                                (size_t)groups * m * n * sizeof(float), st));
   if (lds_bytes > 64 * 1024)
@@ -476,9 +519,7 @@ extern "C" int vtc_fc_dict_apply(float* dictionary, const float* grad_sum,
 extern "C" size_t vtc_code_energy_workspace_bytes(int64_t b, int64_t s,
                                                   int64_t positions) {
   if (b <= 0 || s <= 0) return 256;
-  const int64_t chunks =
-      positions > 1 ? b : ceil_div(b, energy_chunk_rows(b));
-  return align_up((size_t)chunks * s * sizeof(float), 256);
+  return measured_bytes<EnergyLayout>(b, s, positions);
 }
 
 extern "C" int vtc_code_energy(const float* codes, int64_t b, int64_t s,
@@ -493,21 +534,20 @@ extern "C" int vtc_code_energy(const float* codes, int64_t b, int64_t s,
     return VTC_ERR_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
-  float* partial = static_cast<float*>(workspace);
-  int64_t chunks;
+  Carver ws(workspace);
+  const EnergyLayout L(ws, b, s, positions);
+  const int64_t chunks = L.chunks;
   if (positions == 1) {
     const int rows = energy_chunk_rows(b);
-    chunks = ceil_div(b, rows);
     hipLaunchKernelGGL(energy_rows_kernel,
                        dim3((unsigned)ceil_div(s, 256), (unsigned)chunks),
-                       dim3(256), 0, st, codes, b, s, rows, partial);
+                       dim3(256), 0, st, codes, b, s, rows, L.partial);
   } else {
-    chunks = b;
     hipLaunchKernelGGL(energy_maps_kernel, dim3((unsigned)(b * s)), dim3(256),
-                       0, st, codes, s, positions, partial);
+                       0, st, codes, s, positions, L.partial);
   }
   VTC_LAUNCH_CHECK();
-  return launch_slab_reduce(partial, (int)chunks, s, energy, st);
+  return launch_slab_reduce(L.partial, (int)chunks, s, energy, st);
 }
 
 extern "C" int vtc_hessian_ema(float* hessian_diagonal, const float* energy,
@@ -523,9 +563,7 @@ extern "C" int vtc_hessian_ema(float* hessian_diagonal, const float* energy,
 
 extern "C" size_t vtc_ica_moment_workspace_bytes(int64_t b, int64_t s) {
   if (b <= 0 || s <= 0) return 256;
-  return align_up((size_t)b * s * sizeof(float), 256) +
-         align_up((size_t)gradient_slices(b, s, s) * s * s * sizeof(float),
-                  256);
+  return measured_bytes<IcaMomentLayout>(b, s);
 }
 
 extern "C" int vtc_ica_moment(const float* codes, float* moment_sum, int64_t b,
@@ -539,24 +577,22 @@ extern "C" int vtc_ica_moment(const float* codes, float* moment_sum, int64_t b,
   }
   hipStream_t st = as_stream(stream);
   Carver ws(workspace);
-  float* S = ws.take<float>((size_t)b * s);
+  const IcaMomentLayout L(ws, b, s);
   const int slices = gradient_slices(b, s, s);
-  float* slabs = ws.take<float>((size_t)slices * s * s);
   hipLaunchKernelGGL(sign_kernel, dim3(stream_grid(b * s)), dim3(256), 0, st,
-                     codes, S, b * s);
+                     codes, L.S, b * s);
   VTC_LAUNCH_CHECK();
   // M = C^T sign(C), K = b split into slabs summed in a fixed order
-  EpiSlab e{slabs, s * s, s};
-  int rc = launch_gemm_f32<false, false>(codes, s, S, s, s, s, b, slices, e,
+  EpiSlab e{L.slabs, s * s, s};
+  int rc = launch_gemm_f32<false, false>(codes, s, L.S, s, s, s, b, slices, e,
                                          st);
   if (rc != VTC_OK) return rc;
-  return launch_slab_reduce(slabs, slices, s * s, moment_sum, st);
+  return launch_slab_reduce(L.slabs, slices, s * s, moment_sum, st);
 }
 
 extern "C" size_t vtc_ica_apply_workspace_bytes(int64_t s, int64_t n) {
   if (s <= 0 || n <= 0) return 256;
-  return align_up((size_t)s * s * sizeof(float), 256) +
-         align_up((size_t)s * n * sizeof(float), 256);
+  return measured_bytes<IcaApplyLayout>(s, n);
 }
 
 extern "C" int vtc_ica_apply(float* dictionary, const float* moment_sum,
@@ -571,17 +607,16 @@ extern "C" int vtc_ica_apply(float* dictionary, const float* moment_sum,
   }
   hipStream_t st = as_stream(stream);
   Carver ws(workspace);
-  float* T = ws.take<float>((size_t)s * s);
-  float* U = ws.take<float>((size_t)s * n);
+  const IcaApplyLayout L(ws, s, n);
   hipLaunchKernelGGL(ica_center_kernel, dim3(stream_grid(s * s)), dim3(256), 0,
-                     st, moment_sum, T, (float)global_batch, s);
+                     st, moment_sum, L.T, (float)global_batch, s);
   VTC_LAUNCH_CHECK();
-  EpiStore e{U, n};
-  int rc = launch_gemm_f32<true, false>(T, s, dictionary, n, s, n, s, 1, e,
+  EpiStore e{L.U, n};
+  int rc = launch_gemm_f32<true, false>(L.T, s, dictionary, n, s, n, s, 1, e,
                                         st);
   if (rc != VTC_OK) return rc;
   hipLaunchKernelGGL(axpy_rn_kernel, dim3(stream_grid(s * n)), dim3(256), 0,
-                     st, dictionary, U, stepsize, s * n);
+                     st, dictionary, L.U, stepsize, s * n);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }

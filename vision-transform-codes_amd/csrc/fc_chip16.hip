@@ -26,8 +26,19 @@ bool chip16_shape_supported(int64_t n, int64_t s) {
          (n == 64 && (s == 256 || s == 512));
 }
 
+// Scratch of the on-chip kernel: the dictionary in MFMA operand order
+// (chip16_pack_kernel).  One more piece has always been counted and is not
+// used; it stays so that the queried size does not move.
+struct Chip16Layout {
+  float4* packA;
+  Chip16Layout(Carver& ws, int64_t n, int64_t s) {
+    packA = ws.take<float4>((size_t)s * n / 4);
+    ws.take<char>(256);
+  }
+};
+
 size_t chip16_workspace_bytes(int64_t n, int64_t s) {
-  return chip16_shape_supported(n, s) ? align_up((size_t)s * n * 4, 256) + 256
+  return chip16_shape_supported(n, s) ? measured_bytes<Chip16Layout>(n, s)
                                       : 256;
 }
 
@@ -163,10 +174,7 @@ __global__ __launch_bounds__(256) void fc_chip16_kernel(Chip16Params P) {
 
 template <int NT, int ST, int MODE>
 static int launch_chip16(const Chip16Params& P, hipStream_t st) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess)
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
-                                dev);
+  const int cus = compute_units();
   const int64_t tasks = (P.b + 15) / 16;
   int64_t blocks = (tasks + 3) / 4;
   if (blocks > (int64_t)cus) blocks = cus;
@@ -207,7 +215,8 @@ int run_chip16(const float* images, const float* dictionary,
               "the device");
     return VTC_ERR_HIP;
   }
-  float4* packA = static_cast<float4*>(workspace);
+  Carver ws(workspace);
+  float4* packA = Chip16Layout(ws, n, s).packA;
   hipLaunchKernelGGL(chip16_pack_kernel, dim3(128), dim3(256), 0, st,
                      dictionary, packA, (int)s, (int)n);
   VTC_LAUNCH_CHECK();

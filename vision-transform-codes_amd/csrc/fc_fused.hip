@@ -353,7 +353,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
         for (int part = 0; part < NP; ++part)
           a[part] = pipe ? ring[part][i % RING] : VTC_LOAD_T(part, p, nb, ks);
         Racc[nb] = VTC_MFMA(a[0], yb[0], Racc[nb]);
-        if (NP == 2) {
+        if constexpr (NP == 2) {
           Racc[nb] = VTC_MFMA(a[0], yb[1], Racc[nb]);
           Racc[nb] = VTC_MFMA(a[1], yb[0], Racc[nb]);
         }
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
               Rx + part * kRxPart + rx_rd + 32 * (i + 1));
       }
       G = VTC_MFMA(ring[0][i % RING], rb[0], G);
-      if (NP == 2) {
+      if constexpr (NP == 2) {
         G = VTC_MFMA(ring[0][i % RING], rb[1], G);
         G = VTC_MFMA(ring[1][i % RING], rb[0], G);
       }
@@ -657,21 +657,6 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
 
 }  // namespace vtc
 
-// Experiments kept out of the library (profiles/r03_fused_onepacking.txt).
-// Eight waves per workgroup (two per SIMD, 16-atom step-1 tiles): build with
-// -DVTC_EXPERIMENT_EIGHT_WAVES, run with VTC_FUSED_8W=1.
-#ifdef VTC_EXPERIMENT_EIGHT_WAVES
-#include "../../tools/micro/fc_fused8.h"
-#endif
-
-// Experiment kept out of the library (profiles/r03_fused_onepacking.txt): a
-// variant that keeps part of each phase's dictionary tile in LDS and reads it
-// back transposed instead of streaming packT.  Build with
-// -DVTC_EXPERIMENT_ONE_PACKING, run with VTC_FUSED_1P=2|3.
-#ifdef VTC_EXPERIMENT_ONE_PACKING
-#include "../../tools/micro/fc_fused1p.h"
-#endif
-
 namespace vtc {
 
 // -------------------------------------------------------------------- host
@@ -686,12 +671,26 @@ bool fused_shape_supported(int64_t b, int64_t n, int64_t s, int precision) {
          precision == VTC_F16X3;
 }
 
-static size_t pack_bytes(int64_t s) { return (size_t)s * kFN * 2; }
+// operand parts of a precision: bf16 packs hi only, the split modes hi and lo
+static int fused_parts(int precision) { return precision == VTC_BF16 ? 1 : 2; }
+
+// Scratch of the fused kernel: per part the dictionary packed for step 1 and
+// for step 3, then {sigma_D, 1 / sigma_D} of the f16 split.
+struct FusedLayout {
+  unsigned short* packs[4] = {nullptr, nullptr, nullptr, nullptr};
+  float* dscale;
+  FusedLayout(Carver& ws, int64_t s, int parts) {
+    for (int part = 0; part < parts; ++part) {
+      packs[2 * part] = ws.take<unsigned short>((size_t)s * kFN);
+      packs[2 * part + 1] = ws.take<unsigned short>((size_t)s * kFN);
+    }
+    dscale = ws.take<float>(2);
+  }
+};
 
 size_t fused_workspace_bytes(int64_t b, int64_t n, int64_t s, int precision) {
   if (!fused_shape_supported(b, n, s, precision)) return 256;
-  const int parts = (precision == VTC_BF16) ? 1 : 2;
-  return (size_t)parts * 2 * align_up(pack_bytes(s), 256) + 256;
+  return measured_bytes<FusedLayout>(s, fused_parts(precision));
 }
 
 template <int NPH, int NP, int MODE, bool F16>
@@ -745,164 +744,9 @@ static int launch_stamped(FusedParams P, hipStream_t st) {
   return VTC_OK;
 }
 
-#ifdef VTC_EXPERIMENT_ONE_PACKING
-// One-packing variant (fc_fused1p.h), three-product modes.
-template <int NPH, int MODE, bool F16, int NT>
-static int launch_fused1p(const FusedParams& P, hipStream_t st) {
-  using L = Fused1pLds<NT>;
-  auto kernel = fused1p_kernel<NPH, MODE, F16, NT>;
-  static unsigned long long configured = 0;
-  if (first_use_on_this_device(&configured)) {
-    VTC_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, L::total));
-  }
-  const unsigned grid = (unsigned)ceil_div(P.b, kFP);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), L::total, st, P);
-  VTC_LAUNCH_CHECK();
-  return VTC_OK;
-}
-
-template <int NPH, bool F16, int NT>
-static int launch_stamped1p(FusedParams P, hipStream_t st) {
-  using L = Fused1pLds<NT>;
-  auto kernel = fused1p_kernel<NPH, VTC_SOFT, F16, NT, true>;
-  unsigned long long* dev = nullptr;
-  VTC_HIP_CHECK(hipMalloc(&dev, 8 * sizeof(unsigned long long)));
-  VTC_HIP_CHECK(hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), st));
-  VTC_HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(kernel),
-      hipFuncAttributeMaxDynamicSharedMemorySize, L::total));
-  P.stamps = dev;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(P.b, kFP)), dim3(256),
-                     L::total, st, P);
-  VTC_LAUNCH_CHECK();
-  unsigned long long host[8];
-  VTC_HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost,
-                               st));
-  VTC_HIP_CHECK(hipStreamSynchronize(st));
-  VTC_HIP_CHECK(hipFree(dev));
-  const char* names[5] = {"step1", "epilogue", "barrier1", "step3",
-                          "barrier2+x"};
-  double total = 0;
-  for (int k = 0; k < 5; ++k) total += (double)host[k];
-  const double per = (double)host[7] * P.num_iters * NPH;
-  for (int k = 0; k < 5; ++k)
-    fprintf(stderr, "[vtc stamps 1p] %-10s %5.1f%%  %8.0f cycles/phase/wave\n",
-            names[k], 100.0 * host[k] / total, host[k] / per);
-  return VTC_OK;
-}
-
-template <int NPH, bool F16>
-static int dispatch_mode1p(const FusedParams& P, int threshold, int nt,
-                           hipStream_t st) {
-  static const bool stamps = getenv("VTC_FUSED_STAMPS") != nullptr;
-  if (stamps && threshold == VTC_SOFT && NPH == 8)
-    return nt == 2 ? launch_stamped1p<NPH, F16, 2>(P, st)
-                   : launch_stamped1p<NPH, F16, 3>(P, st);
-#define VTC1_CASE(M)                                              \
-  case M:                                                         \
-    return nt == 2 ? launch_fused1p<NPH, M, F16, 2>(P, st)        \
-                   : launch_fused1p<NPH, M, F16, 3>(P, st);
-  switch (threshold) {
-    VTC1_CASE(VTC_SOFT)
-    VTC1_CASE(VTC_SOFT_NONNEG)
-    VTC1_CASE(VTC_HARD)
-    default:
-      return nt == 2 ? launch_fused1p<NPH, VTC_HARD_NONNEG, F16, 2>(P, st)
-                     : launch_fused1p<NPH, VTC_HARD_NONNEG, F16, 3>(P, st);
-  }
-#undef VTC1_CASE
-}
-
-#endif
-
-#ifdef VTC_EXPERIMENT_EIGHT_WAVES
-// Eight-wave form (tools/micro/fc_fused8.h), three-product modes.
-static bool fused_eight_waves() {
-  static const bool on = [] {
-    const char* v = getenv("VTC_FUSED_8W");
-    return v != nullptr && atoi(v) != 0;
-  }();
-  return on;
-}
-
-template <int NPH, int MODE, bool F16>
-static int launch_fused8(const FusedParams& P, hipStream_t st) {
-  using L = Fused8Lds<NPH>;
-  auto kernel = fused8_kernel<NPH, MODE, F16>;
-  static unsigned long long configured = 0;
-  if (first_use_on_this_device(&configured)) {
-    VTC_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, L::total));
-  }
-  const unsigned grid = (unsigned)ceil_div(P.b, kFP);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), L::total, st, P);
-  VTC_LAUNCH_CHECK();
-  return VTC_OK;
-}
-
-template <int NPH, bool F16>
-static int launch_stamped8(FusedParams P, hipStream_t st) {
-  using L = Fused8Lds<NPH>;
-  auto kernel = fused8_kernel<NPH, VTC_SOFT, F16, true>;
-  unsigned long long* dev = nullptr;
-  VTC_HIP_CHECK(hipMalloc(&dev, 8 * sizeof(unsigned long long)));
-  VTC_HIP_CHECK(hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), st));
-  VTC_HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(kernel),
-      hipFuncAttributeMaxDynamicSharedMemorySize, L::total));
-  P.stamps = dev;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(P.b, kFP)), dim3(512),
-                     L::total, st, P);
-  VTC_LAUNCH_CHECK();
-  unsigned long long host[8];
-  VTC_HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost,
-                               st));
-  VTC_HIP_CHECK(hipStreamSynchronize(st));
-  VTC_HIP_CHECK(hipFree(dev));
-  const char* names[5] = {"step1+epi", "epi-alone", "barrier", "step3",
-                          "exchange"};
-  double total = 0;
-  for (int k = 0; k < 5; ++k) total += (double)host[k];
-  const double per = (double)host[7] * P.num_iters * NPH;
-  for (int k = 0; k < 5; ++k)
-    fprintf(stderr, "[vtc stamps 8w] %-9s %5.1f%%  %8.0f cycles/phase/wave\n",
-            names[k], 100.0 * host[k] / total, host[k] / per);
-  fprintf(stderr, "[vtc stamps 8w] barrier wait of waves 0-3: %.0f, of waves "
-          "4-7: %.0f cycles/phase/wave\n", 2.0 * host[5] / per,
-          2.0 * host[6] / per);
-  return VTC_OK;
-}
-
-template <int NPH, bool F16>
-static int dispatch_mode8(const FusedParams& P, int threshold, hipStream_t st) {
-  static const bool stamps = getenv("VTC_FUSED_STAMPS") != nullptr;
-  if (stamps && threshold == VTC_SOFT && NPH == 8)
-    return launch_stamped8<NPH, F16>(P, st);
-  switch (threshold) {
-    case VTC_SOFT: return launch_fused8<NPH, VTC_SOFT, F16>(P, st);
-    case VTC_SOFT_NONNEG: return launch_fused8<NPH, VTC_SOFT_NONNEG, F16>(P, st);
-    case VTC_HARD: return launch_fused8<NPH, VTC_HARD, F16>(P, st);
-    default: return launch_fused8<NPH, VTC_HARD_NONNEG, F16>(P, st);
-  }
-}
-#endif
-
 template <int NPH, int NP, bool F16>
 static int dispatch_mode(const FusedParams& P, int threshold, hipStream_t st) {
   static const bool stamps = getenv("VTC_FUSED_STAMPS") != nullptr;
-#ifdef VTC_EXPERIMENT_EIGHT_WAVES
-  if (NP == 2 && fused_eight_waves())
-    return dispatch_mode8<NPH, F16>(P, threshold, st);
-#endif
-#ifdef VTC_EXPERIMENT_ONE_PACKING
-  static const int one_packing =
-      getenv("VTC_FUSED_1P") ? atoi(getenv("VTC_FUSED_1P")) : 0;
-  if (NP == 2 && one_packing >= 2)
-    return dispatch_mode1p<NPH, F16>(P, threshold, one_packing, st);
-#endif
   if (stamps && threshold == VTC_SOFT && NPH == 8 && NP == 2)
     return launch_stamped<NPH, NP, F16>(P, st);
   switch (threshold) {
@@ -979,16 +823,13 @@ int run_fused(const float* images, const float* dictionary,
     set_error("fused FISTA: could not place the momentum table on the device");
     return VTC_ERR_HIP;
   }
-  const int parts = (precision == VTC_BF16) ? 1 : 2;
+  const int parts = fused_parts(precision);
   const bool f16 = (precision == VTC_F16X3);
   Carver ws(workspace);
   FusedParams P;
-  unsigned short* packs[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int part = 0; part < parts; ++part) {
-    packs[2 * part] = ws.take<unsigned short>((size_t)s * kFN);
-    packs[2 * part + 1] = ws.take<unsigned short>((size_t)s * kFN);
-  }
-  float* dscale = ws.take<float>(2);
+  const FusedLayout L(ws, s, parts);
+  unsigned short* const* packs = L.packs;
+  float* dscale = L.dscale;
   if (f16) {
     hipLaunchKernelGGL(dictionary_scale_kernel, dim3(1), dim3(1024), 0, st,
                        dictionary, (int64_t)s * kFN, dscale);
@@ -1003,18 +844,6 @@ int run_fused(const float* images, const float* dictionary,
                        st, dictionary, (int)s, packs[0], packs[1], packs[2],
                        packs[3], dscale);
   VTC_LAUNCH_CHECK();
-#ifdef VTC_EXPERIMENT_EIGHT_WAVES
-  if (parts == 2 && fused_eight_waves()) {
-    // the eight-wave kernel reads its step-1 operand as 16-atom tiles
-    if (f16)
-      hipLaunchKernelGGL(pack_dictionary8_kernel<true>, dim3(256), dim3(256), 0,
-                         st, dictionary, (int)s, packs[0], packs[2], dscale);
-    else
-      hipLaunchKernelGGL(pack_dictionary8_kernel<false>, dim3(256), dim3(256),
-                         0, st, dictionary, (int)s, packs[0], packs[2], dscale);
-    VTC_LAUNCH_CHECK();
-  }
-#endif
   P.images = images;
   P.init = initial_codes;
   P.codes = codes;

@@ -92,20 +92,8 @@ void fista_betas(int num_iters, std::vector<float>* out) {
 int launch_transpose(const float* in, float* out, int64_t rows, int64_t cols,
                      hipStream_t st);  // subspace.hip
 
-// f16x3 scale state of the tiled path (x3_scale.h): {sigma_D, 1 / sigma_D} and
-// two slots each for max |Y| and max |R|
-constexpr int kX3StateWords = 64 + 4 * kCxMaxSlotWords;
-
 static size_t generic_workspace_bytes(int64_t b, int64_t n, int64_t s) {
-  size_t bytes = 0;
-  bytes += 3 * align_up((size_t)b * s * sizeof(float), 256);  // Y, Y', C'
-  bytes += align_up((size_t)b * n * sizeof(float), 256);  // R
-  bytes += align_up((size_t)s * n * sizeof(float), 256);  // D^T (bf16x3)
-  bytes += align_up((size_t)gemm_x3_want_slices(b, n, s) * b * n *
-                        sizeof(float), 256);  // split-K slabs
-  bytes += 256;                                           // stop accumulator
-  bytes += align_up(kX3StateWords * sizeof(unsigned), 256);  // f16x3 scales
-  return bytes;
+  return measured_bytes<TiledIstaLayout>(b, n, s);
 }
 
 // x3 = false: exact-f32 MFMA; x3 = true: hi/lo split tiles (gemm_x3.h), the
@@ -125,15 +113,12 @@ static int run_generic(const float* images, const float* dictionary,
     return VTC_ERR_WORKSPACE;
   }
   Carver ws(workspace);
-  float* Ybuf = ws.take<float>((size_t)b * s);
-  float* Yalt = ws.take<float>((size_t)b * s);   // out-of-place targets of the
-  float* Calt = ws.take<float>((size_t)b * s);   // proximal epilogue
-  float* R = ws.take<float>((size_t)b * n);
-  float* Dt = ws.take<float>((size_t)s * n);
+  const TiledIstaLayout L(ws, b, n, s);
+  float* R = L.R;
+  float* Dt = L.Dt;
   const int k1_slices = x3 ? gemm_x3_want_slices(b, n, s) : 1;
-  float* slabs = ws.take<float>((size_t)gemm_x3_want_slices(b, n, s) * b * n);
-  double* delta_sum = ws.take<double>(1);
-  unsigned* state = ws.take<unsigned>(kX3StateWords);
+  double* delta_sum = L.delta_sum;
+  unsigned* state = L.state;
   f16 = f16 && x3;
   float* dscale = f16 ? reinterpret_cast<float*>(state) : nullptr;
   unsigned* y_slot[2] = {state + 64, state + 64 + kCxMaxSlotWords};
@@ -153,7 +138,7 @@ static int run_generic(const float* images, const float* dictionary,
   }
 
   const bool fista = (variant == VTC_FISTA);
-  float* Y = fista ? Ybuf : codes;  // ISTA evaluates the gradient at the codes
+  float* Y = fista ? L.Y : codes;  // ISTA evaluates the gradient at the codes
   if (x3) {
     if (!gemm_x3_usable(Y, s, Dt, s) || !gemm_x3_usable(R, n, dictionary, n)) {
       set_error("vtc_fc_ista_fista: bf16x3 outside the fused kernel needs n "
@@ -179,8 +164,8 @@ static int run_generic(const float* images, const float* dictionary,
   fista_betas(num_iters, &betas);
   int done = 0;
   float* Cin = codes;      // (Y, Cin) are read, (Yout, Cout) written, then the
-  float* Cout = Calt;      // roles swap
-  float* Yout = Yalt;
+  float* Cout = L.Cout;      // roles swap
+  float* Yout = L.Yout;
   for (int k = 0; k < num_iters; ++k) {
     if (!fista) Y = Cin;   // ISTA evaluates the gradient at the codes
     // R = Y D - X : A = Y (b,s) k-contiguous, B = D (s,n) = [K][N]
@@ -198,10 +183,10 @@ static int run_generic(const float* images, const float* dictionary,
     }
     int rc;
     if (x3 && k1_slices > 1) {
-      EpiSlab es{slabs, b * n, n};
+      EpiSlab es{L.slabs, b * n, n};
       rc = launch_gemm_x3(Y, s, Dt, s, b, n, s, es, st, k1_slices, sc1);
       if (rc == VTC_OK)
-        rc = launch_slab_reduce_minus(slabs, k1_slices, b * n, images, R, st,
+        rc = launch_slab_reduce_minus(L.slabs, k1_slices, b * n, images, R, st,
                                       f16 ? r_slot[k & 1] : nullptr);
     } else if (x3 && f16) {
       EpiMinusMax e1m{R, images, n, n, r_slot[k & 1]};

@@ -173,10 +173,7 @@ static int launch_small(const SmallParams& P, hipStream_t st) {
     VTC_HIP_CHECK(hipFuncSetAttribute(
         reinterpret_cast<const void*>(fc_small_kernel<ST, MODE>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess)
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
-                                dev);
+  const int cus = compute_units();
   const int64_t tasks = (P.b + 31) / 32;
   int64_t blocks = (tasks + 3) / 4;
   if (blocks > 2 * (int64_t)cus) blocks = 2 * (int64_t)cus;

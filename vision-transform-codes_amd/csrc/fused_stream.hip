@@ -760,16 +760,30 @@ bool stream_shape_supported(int64_t b, int64_t n, int64_t slots, int64_t m,
   return precision == VTC_BF16X3 || precision == VTC_F16X3;
 }
 
-static size_t stream_state_bytes(int64_t b, int64_t slots) {
-  return (size_t)ceil_div(b, 32) * 32 * slots * sizeof(float);
-}
+// Scratch of the streamed kernel: the two code iterates in state order (the
+// batch rounded up to whole 32-patch tiles), hi and lo dictionary packs (each
+// step 1's operand followed by step 3's), per-patch scales of the f16 split
+// and {sigma_D, 1 / sigma_D}.
+struct StreamLayout {
+  float4* state[2];
+  unsigned short* packs[2];
+  float* patch_scale;
+  float* dscale;
+  StreamLayout(Carver& ws, int64_t b, int64_t slots) {
+    const size_t state_floats = (size_t)ceil_div(b, 32) * 32 * slots;
+    for (int k = 0; k < 2; ++k)
+      state[k] = reinterpret_cast<float4*>(ws.take<float>(state_floats));
+    for (int part = 0; part < 2; ++part)
+      packs[part] = ws.take<unsigned short>(2 * (size_t)slots * kFN);
+    patch_scale = ws.take<float>((size_t)b);
+    dscale = ws.take<float>(2);
+  }
+};
 
 size_t stream_workspace_bytes(int64_t b, int64_t n, int64_t slots,
                               int precision) {
   if (!stream_shape_supported(b, n, slots, 1, precision)) return 256;
-  return 2 * align_up(stream_state_bytes(b, slots), 256) +
-         2 * align_up((size_t)2 * slots * kFN * 2, 256) +
-         align_up((size_t)b * sizeof(float), 256) + 256;
+  return measured_bytes<StreamLayout>(b, slots);
 }
 
 template <int M, int MODE, bool F16>
@@ -835,15 +849,12 @@ int run_stream(const float* images, const float* dictionary,
   const size_t pack_half = (size_t)slots * kFN * 2;
   Carver ws(workspace);
   StreamParams P;
-  P.state[0] = reinterpret_cast<float4*>(
-      ws.take<char>(stream_state_bytes(b, slots)));
-  P.state[1] = reinterpret_cast<float4*>(
-      ws.take<char>(stream_state_bytes(b, slots)));
-  unsigned short* packs[2];
-  for (int part = 0; part < 2; ++part)
-    packs[part] = ws.take<unsigned short>(2 * (size_t)slots * kFN);
-  float* patch_scale = ws.take<float>((size_t)b);
-  float* dscale = ws.take<float>(2);
+  const StreamLayout L(ws, b, slots);
+  P.state[0] = L.state[0];
+  P.state[1] = L.state[1];
+  unsigned short* const* packs = L.packs;
+  float* patch_scale = L.patch_scale;
+  float* dscale = L.dscale;
   if (f16) {
     hipLaunchKernelGGL(dictionary_scale_kernel, dim3(1), dim3(1024), 0, st,
                        dictionary, (int64_t)slots * kFN, dscale);

@@ -292,23 +292,10 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_f32_kernel(GemmArgs g,
   epi.block_end();
 }
 
-static int gemm_compute_units() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
-                                 dev) == hipSuccess && n > 0)
-              ? n
-              : 256;
-  }
-  return cus;
-}
-
 static bool gemm_prefers_small(int64_t M, int64_t N) {
   const int64_t tiles = ceil_div(M, kGemmBM) * ceil_div(N, kGemmBN);
   const double full_tiles = (double)M * (double)N / (kGemmBM * kGemmBN);
-  return tiles <= 8 || full_tiles <= (double)gemm_compute_units();
+  return tiles <= 8 || full_tiles <= (double)compute_units();
 }
 
 static inline int gemm_vec_ok(const float* p, int64_t ld) {

@@ -539,6 +539,34 @@ static inline int gemm_x3_want_slices(int64_t M, int64_t N, int64_t K) {
   return gemm_x3_slices(K, (int)want);
 }
 
+// f16x3 scale state of the tiled paths (x3_scale.h): {sigma_D, 1 / sigma_D} and
+// two slots each for max |Y| and max |R|
+constexpr int kX3StateWords = 64 + 4 * kCxMaxSlotWords;
+
+// Scratch of the tiled ISTA/FISTA routes (fully-connected: s atoms; subspace:
+// s = G*m slots).  Dt, slabs and state serve the split modes only and are
+// carved for every precision, so the addresses do not depend on it.
+struct TiledIstaLayout {
+  float* Y;            // gradient evaluation points (FISTA)
+  float* Yout;         // out-of-place targets of the
+  float* Cout;         // proximal epilogue
+  float* R;            // residual (b, n)
+  float* Dt;           // dictionary transposed (n, s)
+  float* slabs;        // split-K slabs of the residual product
+  double* delta_sum;   // stop accumulator
+  unsigned* state;     // f16x3 scales, kX3StateWords
+  TiledIstaLayout(Carver& ws, int64_t b, int64_t n, int64_t s) {
+    Y = ws.take<float>((size_t)b * s);
+    Yout = ws.take<float>((size_t)b * s);
+    Cout = ws.take<float>((size_t)b * s);
+    R = ws.take<float>((size_t)b * n);
+    Dt = ws.take<float>((size_t)s * n);
+    slabs = ws.take<float>((size_t)gemm_x3_want_slices(b, n, s) * b * n);
+    delta_sum = ws.take<double>(1);
+    state = ws.take<unsigned>(kX3StateWords);
+  }
+};
+
 // out = sum_z slabs[z] - X   (fixed order; the residual of a split-K product)
 // max_out (may be null): x3_scale.h slot that receives max |out|
 int launch_slab_reduce_minus(const float* slabs, int slices, int64_t count,

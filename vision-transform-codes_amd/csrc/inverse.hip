@@ -269,6 +269,16 @@ __global__ __launch_bounds__(kInvMaxN) void lu_solve_kernel(
   }
 }
 
+// Scratch of vtc_mat_inverse: the padded float64 LU factors and the row order
+struct InverseLayout {
+  double* A;
+  int* perm;
+  InverseLayout(Carver& ws, int m) {
+    A = ws.take<double>((size_t)m * m);
+    perm = ws.take<int>(m);
+  }
+};
+
 }  // namespace vtc
 
 using namespace vtc;
@@ -276,9 +286,7 @@ using namespace vtc;
 // ---- C ABI ---------------------------------------------------------------
 extern "C" size_t vtc_mat_inverse_workspace_bytes(int64_t n) {
   if (n <= 0 || n > kInvMaxN) return 256;
-  const int m = inv_padded(n);
-  return align_up((size_t)m * m * sizeof(double), 256) +
-         align_up((size_t)m * sizeof(int), 256);
+  return measured_bytes<InverseLayout>(inv_padded(n));
 }
 
 extern "C" int vtc_mat_inverse(const float* a, int64_t n, float* a_inv,
@@ -301,8 +309,7 @@ extern "C" int vtc_mat_inverse(const float* a, int64_t n, float* a_inv,
   }
   const int m = inv_padded(n);
   Carver carve(workspace);
-  double* A = carve.take<double>((size_t)m * m);
-  int* perm = carve.take<int>(m);
+  const InverseLayout L(carve, m);
   hipStream_t s = as_stream(stream);
   static unsigned long long configured = 0;
   if (first_use_on_this_device(&configured)) {
@@ -312,12 +319,12 @@ extern "C" int vtc_mat_inverse(const float* a, int64_t n, float* a_inv,
         (int)inv_factor_lds_bytes(kInvMaxN)));
   }
   hipLaunchKernelGGL(lu_factor_kernel, dim3(1), dim3(kInvThreads),
-                     inv_factor_lds_bytes(m), s, a, (int)n, m, A, perm,
+                     inv_factor_lds_bytes(m), s, a, (int)n, m, L.A, L.perm,
                      status);
   VTC_LAUNCH_CHECK();
   hipLaunchKernelGGL(lu_solve_kernel, dim3((unsigned)ceil_div(n, kInvCols)),
                      dim3((unsigned)ceil_div(m, 64) * 64), 0, s,
-                     (const double*)A, (const int*)perm, (int)n, m, a_inv);
+                     (const double*)L.A, (const int*)L.perm, (int)n, m, a_inv);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }

@@ -564,13 +564,21 @@ __global__ __launch_bounds__(kLanczosThreads) void lanczos_large_kernel(
   }
 }
 
+// Scratch of the large-matrix Lanczos kernel: its basis vectors
+struct LanczosLayout {
+  float* basis;
+  LanczosLayout(Carver& ws, int64_t n) {
+    basis = ws.take<float>((size_t)kLanczosMaxK * n);
+  }
+};
+
 }  // namespace vtc
 
 using namespace vtc;
 
 extern "C" size_t vtc_lambda_max_workspace_bytes(int64_t n) {
   if (n <= kLanczosMaxN || n > kLanczosLargeN) return 256;
-  return align_up((size_t)kLanczosMaxK * n * sizeof(float), 256);
+  return measured_bytes<LanczosLayout>(n);
 }
 
 // out: 3 floats on the device: [lambda_max, 1/lambda_max, converged (1 / 0)]
@@ -590,9 +598,10 @@ static int lambda_max_impl(const float* symmetric, int64_t n, float* out,
       set_error("vtc_lambda_max: workspace too small");
       return VTC_ERR_WORKSPACE;
     }
+    Carver ws(workspace);
     hipLaunchKernelGGL(lanczos_large_kernel, dim3(1), dim3(kLanczosThreads), 0,
                        as_stream(stream), symmetric, (int)n, k,
-                       static_cast<float*>(workspace), out, mirror);
+                       LanczosLayout(ws, n).basis, out, mirror);
     VTC_LAUNCH_CHECK();
     return VTC_OK;
   }

@@ -338,6 +338,25 @@ row_center_kernel(const T* __restrict__ x, int64_t rows, int64_t cols,
   for (int64_t j = lane; j < cols; j += 64) orow[j] = sub_rn(as_f32(xr[j]), m);
 }
 
+// Scratch of the separable route of vtc_local_normalize: one float64 plane
+// per image channel (the row pass), size published without padding
+struct LocalNormLayout {
+  double* rows_pass;
+  LocalNormLayout(Carver& ws, int64_t count, int32_t h, int32_t w, int32_t c) {
+    rows_pass = ws.take_unpadded<double>((size_t)count * h * w * c);
+  }
+};
+
+// Scratch of vtc_column_moments: per slab and column the partial sum and sum
+// of squares, size published without padding
+struct MomentsLayout {
+  double* partial;
+  MomentsLayout(Carver& ws, int64_t rows, int64_t cols) {
+    partial = ws.take_unpadded<double>((size_t)moment_slabs(rows, cols) *
+                                       cols * 2);
+  }
+};
+
 }  // namespace
 
 }  // namespace vtc
@@ -352,7 +371,7 @@ extern "C" size_t vtc_local_normalize_workspace_bytes(int64_t count,
   const int n = gaussian_tap_count(filter_sigma, &lower);
   if (n <= 0 || count <= 0 || h <= 0 || w <= 0 || c <= 0) return 0;
   if (-lower <= kTileRadius) return 0;
-  return (size_t)count * h * w * c * sizeof(double);
+  return measured_bytes<LocalNormLayout>(count, h, w, c);
 }
 
 extern "C" int vtc_local_normalize(const float* images, float* out, float* aux,
@@ -390,7 +409,8 @@ extern "C" int vtc_local_normalize(const float* images, float* out, float* aux,
     VTC_LAUNCH_CHECK();
     return VTC_OK;
   }
-  double* ws = static_cast<double*>(workspace);
+  Carver carve(workspace);
+  double* ws = LocalNormLayout(carve, count, h, w, c).rows_pass;
   hipLaunchKernelGGL(local_norm_rows_kernel, dim3(grid_for(total)), dim3(256),
                      0, as_stream(stream), images, ws, total, w, c, mode,
                      taps);
@@ -405,7 +425,7 @@ extern "C" int vtc_local_normalize(const float* images, float* out, float* aux,
 extern "C" size_t vtc_column_moments_workspace_bytes(int64_t rows,
                                                      int64_t cols) {
   if (rows <= 0 || cols <= 0) return 0;
-  return (size_t)moment_slabs(rows, cols) * cols * 2 * sizeof(double);
+  return measured_bytes<MomentsLayout>(rows, cols);
 }
 
 extern "C" int vtc_column_moments(const void* x, int dtype, int64_t rows,
@@ -426,7 +446,8 @@ extern "C" int vtc_column_moments(const void* x, int dtype, int64_t rows,
   const int64_t slabs = moment_slabs(rows, cols);
   const int64_t slab_rows = ceil_div(rows, slabs);
   const dim3 grid((unsigned)ceil_div(cols, kMomCols), (unsigned)slabs);
-  double* partial = static_cast<double*>(workspace);
+  Carver carve(workspace);
+  double* partial = MomentsLayout(carve, rows, cols).partial;
   const unsigned fin = (unsigned)ceil_div(cols, 256);
   if (dtype == VTC_DTYPE_F32) {
     const float* p = static_cast<const float*>(x);

@@ -129,6 +129,15 @@ __global__ __launch_bounds__(kStatThreads) void rows_mean_abs_diff_kernel(
 
 constexpr int kMinMaxBlocks = 512;
 
+// Scratch of vtc_window_minmax: {min, max} per block, size published without
+// padding
+struct MinMaxLayout {
+  float* partial;
+  explicit MinMaxLayout(Carver& ws) {
+    partial = ws.take_unpadded<float>((size_t)kMinMaxBlocks * 2);
+  }
+};
+
 }  // namespace vtc
 
 using namespace vtc;
@@ -164,7 +173,7 @@ extern "C" int vtc_group_norm_sum(const float* codes, const int32_t* index,
 }
 
 extern "C" size_t vtc_window_minmax_workspace_bytes(void) {
-  return (size_t)kMinMaxBlocks * 2 * sizeof(float);
+  return measured_bytes<MinMaxLayout>();
 }
 
 extern "C" int vtc_window_minmax(const float* x, int64_t outer, int64_t rows,
@@ -182,7 +191,8 @@ extern "C" int vtc_window_minmax(const float* x, int64_t outer, int64_t rows,
   const int64_t total = outer * rows * cols;
   int64_t blocks = ceil_div(total, kStatThreads);
   if (blocks > kMinMaxBlocks) blocks = kMinMaxBlocks;
-  float* partial = static_cast<float*>(workspace);
+  Carver ws(workspace);
+  float* partial = MinMaxLayout(ws).partial;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(window_minmax_partial_kernel, dim3((unsigned)blocks),
                      dim3(kStatThreads), 0, st, x, outer, rows, cols,

@@ -285,6 +285,20 @@ __global__ __launch_bounds__(256) void extract_patches_kernel(
   }
 }
 
+// Scratch of vtc_whiten_center_surround: the float64 planes, their half
+// spectra and, with norm_and_threshold, the maximum of the transfer function.
+struct WhitenLayout {
+  double* real;
+  hipfftDoubleComplex* spec;
+  unsigned long long* gain_max = nullptr;
+  WhitenLayout(Carver& ws, int64_t planes, int32_t h, int32_t w,
+               bool norm_and_threshold) {
+    real = ws.take<double>((size_t)planes * h * w);
+    spec = ws.take<hipfftDoubleComplex>((size_t)planes * h * (w / 2 + 1));
+    if (norm_and_threshold) gain_max = ws.take<unsigned long long>(1);
+  }
+};
+
 }  // namespace vtc
 
 using namespace vtc;
@@ -294,10 +308,7 @@ extern "C" size_t vtc_whiten_center_surround_workspace_bytes(int64_t count,
                                                              int32_t w,
                                                              int32_t c) {
   if (count <= 0 || h <= 0 || w <= 0 || c <= 0) return 256;
-  const size_t planes = (size_t)count * c;
-  return align_up(planes * h * w * sizeof(double), 256) +
-         align_up(planes * h * (w / 2 + 1) * sizeof(hipfftDoubleComplex), 256) +
-         256;   // maximum of the transfer function (norm_and_threshold)
+  return measured_bytes<WhitenLayout>(count * c, h, w, true);
 }
 
 extern "C" int vtc_whiten_center_surround(const float* images, float* out,
@@ -327,17 +338,15 @@ extern "C" int vtc_whiten_center_surround(const float* images, float* out,
   const FftApi& api = fft_api();
   hipStream_t st = as_stream(stream);
   Carver ws(workspace);
-  double* real = ws.take<double>((size_t)planes * h * w);
-  hipfftDoubleComplex* spec =
-      ws.take<hipfftDoubleComplex>((size_t)planes * h * (w / 2 + 1));
-  unsigned long long* gain_max = nullptr;
+  const WhitenLayout L(ws, planes, h, w, norm_and_threshold != 0);
+  double* real = L.real;
   if (norm_and_threshold) {
-    gain_max = ws.take<unsigned long long>(1);
-    VTC_HIP_CHECK(hipMemsetAsync(gain_max, 0, sizeof(unsigned long long), st));
+    VTC_HIP_CHECK(hipMemsetAsync(L.gain_max, 0, sizeof(unsigned long long),
+                                 st));
     hipLaunchKernelGGL(whitening_gain_max_kernel,
                        dim3(flat_grid((int64_t)h * (w / 2 + 1))), dim3(256), 0,
                        st, h, w, (double)cutoff_low, (double)cutoff_high,
-                       gain_max);
+                       L.gain_max);
     VTC_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(planes_from_images_kernel,
@@ -346,16 +355,16 @@ extern "C" int vtc_whiten_center_surround(const float* images, float* out,
   VTC_LAUNCH_CHECK();
   if (api.set_stream(plans.forward, st) != HIPFFT_SUCCESS ||
       api.set_stream(plans.inverse, st) != HIPFFT_SUCCESS ||
-      api.exec_d2z(plans.forward, real, spec) != HIPFFT_SUCCESS) {
+      api.exec_d2z(plans.forward, real, L.spec) != HIPFFT_SUCCESS) {
     set_error("vtc_whiten_center_surround: forward transform failed");
     return VTC_ERR_HIP;
   }
   hipLaunchKernelGGL(whitening_filter_kernel,
                      dim3(flat_grid(planes * h * (w / 2 + 1))), dim3(256), 0,
-                     st, spec, planes, h, w, (double)cutoff_low,
-                     (double)cutoff_high, gain_max);
+                     st, L.spec, planes, h, w, (double)cutoff_low,
+                     (double)cutoff_high, L.gain_max);
   VTC_LAUNCH_CHECK();
-  if (api.exec_z2d(plans.inverse, spec, real) != HIPFFT_SUCCESS) {
+  if (api.exec_z2d(plans.inverse, L.spec, real) != HIPFFT_SUCCESS) {
     set_error("vtc_whiten_center_surround: inverse transform failed");
     return VTC_ERR_HIP;
   }

@@ -1,9 +1,9 @@
-// Version / error-string plumbing of libvtc_hip.
+// Version / error-string plumbing of libvtc_hip and the per-device CU count.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/vtc_hip.h"
+#include "common.h"
 
 namespace vtc {
 static thread_local char g_error[512] = "";
@@ -13,6 +13,19 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_error, sizeof(g_error), fmt, ap);
   va_end(ap);
+}
+
+int compute_units() {
+  constexpr int kMaxDevices = 64;
+  static int cached[kMaxDevices] = {0};   // 0: not asked yet
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices)
+    return 256;
+  if (cached[dev] == 0)
+    cached[dev] = (hipDeviceGetAttribute(
+                       &n, hipDeviceAttributeMultiprocessorCount, dev) ==
+                       hipSuccess && n > 0) ? n : 256;
+  return cached[dev];
 }
 }  // namespace vtc
 

@@ -249,17 +249,8 @@ static bool launch_group_prox_pow2(float* Y, float* C, int64_t b,
   return false;
 }
 
-// f16x3 scale state of the tiled path (x3_scale.h)
-constexpr int kSubStateWords = 64 + 4 * kCxMaxSlotWords;
-
 static size_t subspace_ws_bytes(int64_t b, int64_t n, int64_t slots) {
-  return 3 * align_up((size_t)b * slots * sizeof(float), 256) +  // Y, Y', C'
-         align_up((size_t)b * n * sizeof(float), 256) +       // R
-         align_up((size_t)slots * n * sizeof(float), 256) +   // Dg^T (bf16x3)
-         align_up((size_t)gemm_x3_want_slices(b, n, slots) * b * n *
-                      sizeof(float), 256) +                       // split-K slabs
-         align_up(kSubStateWords * sizeof(unsigned), 256) +       // f16 scales
-         256;
+  return measured_bytes<TiledIstaLayout>(b, n, slots);
 }
 
 // out[c][r] = in[r][c]
@@ -399,18 +390,18 @@ extern "C" int vtc_subspace_ista_fista(
   }
   hipStream_t st = as_stream(stream);
   Carver ws(workspace);
-  float* Y = ws.take<float>((size_t)b * slots);
-  float* Yout = ws.take<float>((size_t)b * slots);  // out-of-place targets of
-  float* Cout = ws.take<float>((size_t)b * slots);  // the proximal epilogue
+  const TiledIstaLayout L(ws, b, n, slots);
+  float* Y = L.Y;
+  float* Yout = L.Yout;
+  float* Cout = L.Cout;
   float* Cin = grouped_codes;
-  float* R = ws.take<float>((size_t)b * n);
-  float* DgT = ws.take<float>((size_t)slots * n);
+  float* R = L.R;
+  float* DgT = L.Dt;
   const int k1_slices = (precision == VTC_BF16X3)
                             ? gemm_x3_want_slices(b, n, slots)
                             : 1;
-  float* slabs = ws.take<float>((size_t)gemm_x3_want_slices(b, n, slots) * b * n);
-  double* delta_sum = ws.take<double>(1);
-  unsigned* state = ws.take<unsigned>(kSubStateWords);
+  double* delta_sum = L.delta_sum;
+  unsigned* state = L.state;
   const float eta = stepsize;
   const float cutoff = sparsity_weight * stepsize;
   const float eps = early_stopping_epsilon;
@@ -440,7 +431,7 @@ extern "C" int vtc_subspace_ista_fista(
   unsigned* r_slot[2] = {state + 64 + 2 * kCxMaxSlotWords,
                          state + 64 + 3 * kCxMaxSlotWords};
   if (f16) {
-    VTC_HIP_CHECK(hipMemsetAsync(state, 0, kSubStateWords * sizeof(unsigned),
+    VTC_HIP_CHECK(hipMemsetAsync(state, 0, kX3StateWords * sizeof(unsigned),
                                  st));
     hipLaunchKernelGGL(cx_array_scale_kernel, dim3(1), dim3(1024), 0, st,
                        grouped_dictionary, slots * n, dscale);
@@ -479,11 +470,11 @@ extern "C" int vtc_subspace_ista_fista(
     int rc;
     if (x3 && k1_slices > 1) {
       // few output tiles (n is small): split the long slot axis over blocks
-      EpiSlab es{slabs, b * n, n};
+      EpiSlab es{L.slabs, b * n, n};
       rc = launch_gemm_x3(Y, slots, DgT, slots, b, n, slots, es, st,
                           k1_slices, sc1);
       if (rc == VTC_OK)
-        rc = launch_slab_reduce_minus(slabs, k1_slices, b * n, images, R, st,
+        rc = launch_slab_reduce_minus(L.slabs, k1_slices, b * n, images, R, st,
                                       f16 ? r_slot[k & 1] : nullptr);
     } else if (x3 && f16) {
       EpiMinusMax e1m{R, images, n, n, r_slot[k & 1]};

@@ -537,6 +537,33 @@ __global__ __launch_bounds__(256) void row_transform_kernel(
   }
 }
 
+// Scratch of vtc_column_covariance.  own_means: the caller gave no means_f64,
+// the column means live here.  One more piece has always been counted and is
+// not used; it stays so that the queried size does not move.
+struct CovarianceLayout {
+  double* cov_part;
+  double* mean_part;
+  double* means = nullptr;
+  CovarianceLayout(Carver& ws, int64_t rows, int64_t cols, bool own_means) {
+    cov_part = ws.take<double>((size_t)cov_slabs(rows, cols) *
+                               cov_tiles(cols) * kCovTile * kCovTile);
+    mean_part = ws.take<double>((size_t)mean_slabs(rows) * cols);
+    if (own_means) means = ws.take<double>(cols);
+    ws.take<char>(256);
+  }
+};
+
+// Scratch of vtc_sym_eig: the matrix and the rotations, padded to an even order
+struct SymEigLayout {
+  double* A;
+  double* V;
+  SymEigLayout(Carver& ws, int64_t n) {
+    const int64_t m = n + (n & 1);
+    A = ws.take<double>(m * m);
+    V = ws.take<double>(m * m);
+  }
+};
+
 }  // namespace vtc
 
 using namespace vtc;
@@ -545,11 +572,7 @@ using namespace vtc;
 extern "C" size_t vtc_column_covariance_workspace_bytes(int64_t rows,
                                                         int64_t cols) {
   if (rows <= 0 || cols <= 0) return 256;
-  const size_t cov = (size_t)cov_slabs(rows, cols) * cov_tiles(cols) *
-                     kCovTile * kCovTile * sizeof(double);
-  const size_t mean = (size_t)mean_slabs(rows) * cols * sizeof(double);
-  return align_up(cov, 256) + align_up(mean, 256) +
-         align_up((size_t)cols * sizeof(double), 256) + 256;
+  return measured_bytes<CovarianceLayout>(rows, cols, true);
 }
 
 extern "C" int vtc_column_covariance(const float* x, int64_t rows,
@@ -570,9 +593,8 @@ extern "C" int vtc_column_covariance(const float* x, int64_t rows,
   Carver carve(workspace);
   const int64_t cslabs = cov_slabs(rows, cols), tiles = cov_tiles(cols);
   const int64_t mslabs = mean_slabs(rows);
-  double* cov_part = carve.take<double>(cslabs * tiles * kCovTile * kCovTile);
-  double* mean_part = carve.take<double>(mslabs * cols);
-  double* means = means_f64 ? means_f64 : carve.take<double>(cols);
+  const CovarianceLayout L(carve, rows, cols, means_f64 == nullptr);
+  double* means = means_f64 ? means_f64 : L.means;
   hipStream_t s = as_stream(stream);
   const bool need_means = center || means_f64 || grand_mean_f64;
   if (need_means) {
@@ -580,10 +602,10 @@ extern "C" int vtc_column_covariance(const float* x, int64_t rows,
     hipLaunchKernelGGL(column_sum_kernel,
                        dim3((unsigned)ceil_div(cols, kMeanCols),
                             (unsigned)mslabs),
-                       dim3(256), 0, s, x, rows, cols, per, mean_part);
+                       dim3(256), 0, s, x, rows, cols, per, L.mean_part);
     VTC_LAUNCH_CHECK();
     hipLaunchKernelGGL(column_mean_kernel, dim3(1), dim3(256), 0, s,
-                       (const double*)mean_part, mslabs, rows, cols, means,
+                       (const double*)L.mean_part, mslabs, rows, cols, means,
                        grand_mean_f64);
     VTC_LAUNCH_CHECK();
   }
@@ -593,11 +615,11 @@ extern "C" int vtc_column_covariance(const float* x, int64_t rows,
   hipLaunchKernelGGL(covariance_partial_kernel,
                      dim3((unsigned)tiles, (unsigned)slabs),
                      dim3(kCovThreads), 0, s, x, rows, cols, center ? 1 : 0,
-                     (const double*)means, per, cov_part);
+                     (const double*)means, per, L.cov_part);
   VTC_LAUNCH_CHECK();
   hipLaunchKernelGGL(covariance_reduce_kernel,
                      dim3((unsigned)ceil_div(cols * cols, 256)), dim3(256), 0,
-                     s, (const double*)cov_part, slabs, tiles, rows, cols,
+                     s, (const double*)L.cov_part, slabs, tiles, rows, cols,
                      cov_f64);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
@@ -605,8 +627,7 @@ extern "C" int vtc_column_covariance(const float* x, int64_t rows,
 
 extern "C" size_t vtc_sym_eig_workspace_bytes(int64_t n) {
   if (n <= 0 || n > kEigMaxN) return 256;
-  const int64_t m = n + (n & 1);
-  return 2 * align_up((size_t)m * m * sizeof(double), 256);
+  return measured_bytes<SymEigLayout>(n);
 }
 
 extern "C" int vtc_sym_eig(const double* a_f64, int64_t n, int max_sweeps,
@@ -626,11 +647,9 @@ extern "C" int vtc_sym_eig(const double* a_f64, int64_t n, int max_sweeps,
     return VTC_ERR_WORKSPACE;
   }
   Carver carve(workspace);
-  const int64_t m = n + (n & 1);
-  double* A = carve.take<double>(m * m);
-  double* V = carve.take<double>(m * m);
+  const SymEigLayout L(carve, n);
   hipLaunchKernelGGL(jacobi_eig_kernel, dim3(1), dim3(kEigThreads), 0,
-                     as_stream(stream), a_f64, (int)n, max_sweeps, A, V,
+                     as_stream(stream), a_f64, (int)n, max_sweeps, L.A, L.V,
                      eigvals_f64, eigvecs_f32, status);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
