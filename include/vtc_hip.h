@@ -41,6 +41,22 @@
  *   - every pointer is a DEVICE pointer to contiguous row-major float32 unless
  *     said otherwise; sizes are element counts; `stream` is a hipStream_t
  *     passed as void* (NULL = the null stream).
+ *   - alignment: a data pointer needs the alignment of its element and no
+ *     more (4 bytes for float32 / int32, 8 for float64, 1 for the byte
+ *     tables), so a contiguous view at any element offset of a larger buffer
+ *     is a legal argument.  Kernels that move 16 bytes at a time run only when
+ *     every array they touch that way is 16-byte aligned and its row length
+ *     keeps every such access on a 16-byte boundary; otherwise the call
+ *     takes a route of the same workspace query that reads and writes the
+ *     caller's arrays element by element (the exact-f32 tiles and direct
+ *     kernels): same contract, float32-level results, slower.  `workspace`
+ *     must be 256-byte aligned: it is carved into 256-byte aligned pieces
+ *     that the kernels access 16 bytes at a time.  One combination has no
+ *     element-wise route and answers VTC_ERR_UNSUPPORTED, before any device
+ *     work and naming the argument, when images, dictionary, initial_codes
+ *     or codes is not 16-byte aligned: VTC_BF16 of vtc_fc_ista_fista and
+ *     vtc_fc_ista_fista_dev (it exists only as the fused kernel).  No other
+ *     entry point refuses a pointer for its alignment.
  *   - functions only enqueue work on `stream` and return; the single exception
  *     is an inference call with early_stopping_epsilon >= 0, which has to read
  *     one flag back per iteration exactly like the reference's

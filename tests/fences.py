@@ -15,6 +15,12 @@ lands inside it.  That is a condition, not a measurement: a write wilder than
 the guard is long (a wrong base pointer, an index that overflowed) can still
 land beyond it and escape, and a write that happens to store 0xA5 is not seen.
 
+`skew` (0 by default: byte for byte the layout above) starts the payload that
+many bytes further on -- a multiple of the element size below 16 -- so that it
+is NOT 16-byte aligned: the flat buffer grows by `skew` bytes, the leading
+guard with it, and both guards still touch the payload's first and last byte.
+tests/test_pointer_alignment_gpu.py runs the fence table on such payloads.
+
 The module runs on the CPU as well (`self_test`), which is how the suite shows
 that the fences bite without a GPU and without touching product code.
 """
@@ -39,19 +45,28 @@ def guard_bytes(payload_bytes):
 class Fence(object):
   """One [guard | payload | guard] arena.  `payload` is the tensor view."""
 
-  def __init__(self, shape, dtype, device, fill=POISON_BYTE):
+  def __init__(self, shape, dtype, device, fill=POISON_BYTE, skew=0):
     shape = tuple(int(v) for v in (shape if hasattr(shape, '__len__')
                                    else (shape,)))
     self.itemsize = torch.empty((), dtype=dtype).element_size()
     self.nbytes = int(np.prod(shape, dtype=np.int64)) * self.itemsize
     self.guard = guard_bytes(self.nbytes)
     assert self.guard % GUARD_QUANTUM == 0
-    self.flat = torch.full((2 * self.guard + self.nbytes,), GUARD_BYTE,
-                           dtype=torch.uint8, device=device)
-    self.raw = self.flat[self.guard:self.guard + self.nbytes]
+    self.skew = int(skew)
+    assert 0 <= self.skew <= 15 and self.skew % self.itemsize == 0, skew
+    # the payload starts `lead` bytes into the flat buffer, the trailing guard
+    # is `guard` bytes long: [guard + skew | payload | guard]
+    self.lead = self.guard + self.skew
+    self.flat = torch.full((self.lead + self.nbytes + self.guard,),
+                           GUARD_BYTE, dtype=torch.uint8, device=device)
+    self.raw = self.flat[self.lead:self.lead + self.nbytes]
     self.raw.fill_(fill)
     self.payload = self.raw.view(dtype).reshape(shape)
-    assert self.payload.data_ptr() == self.flat.data_ptr() + self.guard
+    assert self.payload.data_ptr() == self.flat.data_ptr() + self.lead
+    assert self.payload.is_contiguous()
+    if self.skew and self.nbytes:
+      assert self.payload.data_ptr() % 16 == (
+          self.flat.data_ptr() + self.skew) % 16
 
   def set(self, value):
     """Copy a same-shaped tensor or array into the payload."""
@@ -65,13 +80,13 @@ class Fence(object):
     offset of the first damaged byte relative to the payload."""
     if self.flat.is_cuda:
       torch.cuda.synchronize(self.flat.device)
-    lead = self.flat[:self.guard]
-    trail = self.flat[self.guard + self.nbytes:]
+    lead = self.flat[:self.lead]
+    trail = self.flat[self.lead + self.nbytes:]
     out = []
     if not bool((lead == GUARD_BYTE).all()):
       bad = torch.nonzero(lead != GUARD_BYTE)
       out.append('leading guard, %d bytes damaged, nearest %d before the '
-                 'payload' % (bad.numel(), self.guard - int(bad.max())))
+                 'payload' % (bad.numel(), self.lead - int(bad.max())))
     if not bool((trail == GUARD_BYTE).all()):
       bad = torch.nonzero(trail != GUARD_BYTE)
       out.append('trailing guard, %d bytes damaged, first %d past the end'
@@ -100,24 +115,31 @@ class Fence(object):
       raise FenceError('%s: payload was written' % what)
 
 
-def fenced(shape, dtype, device, fill=POISON_BYTE):
+def fenced(shape, dtype, device, fill=POISON_BYTE, skew=0):
   """(payload, fence): `payload` is the tensor to hand to the library."""
-  f = Fence(shape, dtype, device, fill)
+  f = Fence(shape, dtype, device, fill, skew)
   return f.payload, f
 
 
-def fenced_copy(value, device):
+def fenced_copy(value, device, skew=0):
   """A fenced arena holding a copy of `value` (tensor or numpy array)."""
   if not torch.is_tensor(value):
     value = torch.from_numpy(np.ascontiguousarray(value))
-  f = Fence(value.shape, value.dtype, device)
+  f = Fence(value.shape, value.dtype, device, skew=skew)
   f.set(value)
   return f.payload, f
 
 
-def fenced_workspace(nbytes, device):
+def fenced_workspace(nbytes, device, skew=0):
   """Scratch of exactly `nbytes` bytes (not rounded up), 0xFF-filled."""
-  return fenced((int(nbytes),), torch.uint8, device)
+  return fenced((int(nbytes),), torch.uint8, device, skew=skew)
+
+
+def skew_for(itemsize, want):
+  """The allowed skew (a multiple of the element size, 1..15 bytes) nearest to
+  `want` bytes; ties go to the smaller one."""
+  allowed = range(itemsize, 16, itemsize)
+  return min(allowed, key=lambda v: (abs(v - want), v))
 
 
 def self_test(device='cpu'):
@@ -131,11 +153,10 @@ def self_test(device='cpu'):
   fence.assert_intact('clean arena')
   fence.assert_written('clean arena')
 
-  for offset, label in ((fence.guard + fence.nbytes, 'one byte past'),
-                        (fence.guard - 1, 'one byte before')):
+  for past, label in ((True, 'one byte past'), (False, 'one byte before')):
     payload, fence = fenced((5, 7), torch.float32, device)
     payload.zero_()
-    fence.flat[offset] = 0
+    fence.flat[fence.guard + fence.nbytes if past else fence.guard - 1] = 0
     try:
       fence.assert_intact(label)
     except FenceError as e:
@@ -162,3 +183,61 @@ def self_test(device='cpu'):
   big = Fence((3 << 20,), torch.uint8, device)
   assert big.guard >= big.nbytes
   return reports
+
+
+def self_test_skewed(device='cpu'):
+  """The same three faults on payloads that start 4, 8 and 12 bytes (float32),
+  8 bytes (float64) and 1, 2, 3 bytes (uint8) past the aligned position.
+  Returns {(dtype name, skew): [past, before, unwritten or None]}."""
+  out = {}
+  for dtype, skews in ((torch.float32, (4, 8, 12)), (torch.float64, (8,)),
+                       (torch.int32, (4,)), (torch.uint8, (1, 2, 3))):
+    for skew in skews:
+      plain = Fence((5, 7), dtype, device)
+      payload, fence = fenced((5, 7), dtype, device, skew=skew)
+      assert payload.is_contiguous() and payload.shape == (5, 7)
+      assert payload.data_ptr() - fence.flat.data_ptr() == plain.guard + skew
+      assert fence.flat.numel() == plain.flat.numel() + skew
+      assert bool((fence.raw == POISON_BYTE).all())
+      # both guards touch the payload
+      assert int(fence.flat[fence.lead - 1]) == GUARD_BYTE
+      assert int(fence.flat[fence.lead + fence.nbytes]) == GUARD_BYTE
+      fence.assert_untouched('fresh skewed arena')
+      payload.zero_()
+      fence.assert_intact('clean skewed arena')
+      if dtype.is_floating_point:
+        fence.assert_written('clean skewed arena')
+      reports = []
+      for offset in (fence.lead + fence.nbytes, fence.lead - 1):
+        payload, fence = fenced((5, 7), dtype, device, skew=skew)
+        payload.zero_()
+        fence.flat[offset] = 0
+        try:
+          fence.assert_intact('skewed')
+        except FenceError as e:
+          reports.append(str(e))
+        else:
+          raise AssertionError('skewed fence missed a write at %d' % offset)
+      unwritten = None
+      if dtype.is_floating_point:
+        payload, fence = fenced((5, 7), dtype, device, skew=skew)
+        payload.zero_()
+        fence.raw[17 * fence.itemsize:18 * fence.itemsize] = POISON_BYTE
+        fence.assert_intact('skewed, unwritten element')
+        try:
+          fence.assert_written('skewed, unwritten element')
+        except FenceError as e:
+          unwritten = str(e)
+        else:
+          raise AssertionError('skewed fence missed an unwritten element')
+      reports.append(unwritten)
+      out[(str(dtype).split('.')[-1], skew)] = reports
+  value = np.arange(35, dtype=np.float32).reshape(5, 7)
+  payload, fence = fenced_copy(value, device, skew=12)
+  assert np.array_equal(payload.cpu().numpy(), value)
+  fence.assert_intact('skewed copy')
+  ws, fence = fenced_workspace(1000, device)
+  assert fence.skew == 0 and fence.lead == fence.guard
+  assert [skew_for(4, 12), skew_for(8, 12), skew_for(1, 12), skew_for(2, 12),
+          skew_for(8, 8), skew_for(4, 8)] == [12, 8, 12, 12, 8, 8]
+  return out

@@ -101,6 +101,31 @@ def test_fences_report_each_deliberate_fault():
   assert 'not written' in reports[2] and 'index 17' in reports[2]
 
 
+def test_skewed_fences_report_each_deliberate_fault():
+  """A payload that starts 1 to 12 bytes past the aligned position keeps both
+  guards against its first and last byte: one damaged byte on either side is
+  seen at the right offset, and so is an element left unwritten."""
+  found = fences.self_test_skewed('cpu')
+  assert sorted(found) == [('float32', 4), ('float32', 8), ('float32', 12),
+                           ('float64', 8), ('int32', 4), ('uint8', 1),
+                           ('uint8', 2), ('uint8', 3)]
+  for (dtype, skew), (past, before, unwritten) in found.items():
+    assert 'trailing guard, 1 bytes damaged, first 0 past the end' in past
+    assert 'leading guard, 1 bytes damaged, nearest 1 before' in before
+    if dtype.startswith('float'):
+      assert 'not written' in unwritten and 'index 17' in unwritten
+    else:
+      assert unwritten is None
+
+
+def test_skew_zero_is_the_old_layout():
+  import torch
+  f = fences.Fence((5, 7), torch.float32, 'cpu')
+  assert f.skew == 0 and f.lead == f.guard
+  assert f.flat.numel() == 2 * f.guard + f.nbytes
+  assert f.payload.data_ptr() == f.flat.data_ptr() + f.guard
+
+
 def test_guard_length_rule():
   for nbytes in (0, 1, 511, 1 << 20, (1 << 20) + 1, 5 << 20):
     g = fences.guard_bytes(nbytes)

@@ -112,10 +112,12 @@ def test_register_resident_kernel_against_the_oracle(device, n, s, b):
   assert torch.equal(a, b2)
 
 
-def test_misaligned_views_fall_back_to_the_tiled_path(device):
-  """The register-resident kernels move patches and codes as float4; a view
-  that starts 4 bytes into its storage takes the tiled path instead (and gives
-  the same codes within the f32 tolerance)."""
+def test_misaligned_views_give_the_same_codes(device):
+  """The register-resident kernels move patches and codes as float4; the
+  plugin hands them an aligned copy of a view that starts 4 bytes into its
+  storage (the C call on such a pointer takes the tiled path:
+  tests/test_pointer_alignment_gpu.py) and the codes hold the f32
+  tolerance."""
   from analysis_transforms.fully_connected import ista_fista
   X, D = _case(11, 100, 64)
   eta = float(sc_oracle.fc_stepsize(torch.from_numpy(D)))

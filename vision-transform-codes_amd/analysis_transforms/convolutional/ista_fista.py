@@ -67,6 +67,25 @@ def run(images_padded, dictionary, kernel_stride, padding_dims,
   iters_run = ctypes.c_int(0)
   eps = -1.0 if early_stopping_epsilon is None else float(
       early_stopping_epsilon)
+  name = _resolve_precision(precision, geom, hard_threshold)
+  vtc_hip.check(lib.vtc_conv_ista_fista(
+      vtc_hip.ptr(images_padded), vtc_hip.ptr(dictionary),
+      vtc_hip.ptr(initial_codes), vtc_hip.ptr(codes), ctypes.byref(geom),
+      float(stepsize), float(sparsity_weight), int(num_iters),
+      vtc_hip.variant_code(variant),
+      vtc_hip.threshold_mode(nonnegative_only, hard_threshold), eps,
+      vtc_hip.PRECISIONS[name], vtc_hip.ptr(ws), ws.numel(), ctypes.byref(iters_run),
+      vtc_hip.current_stream(device)), 'vtc_conv_ista_fista')
+  run.last_iters = iters_run.value
+  return codes
+
+
+def _resolve_precision(precision, geom, hard_threshold):
+  """Name of the precision a call runs in (None: the process-wide default).
+  The choice depends on the geometry alone, never on where the tensors lie:
+  every convolutional kernel reads and writes the caller's arrays one element
+  at a time."""
+  lib = vtc_hip.load_library()
   name = precision if precision is not None else (
       vtc_hip.get_default_precision())
   if name == 'auto':
@@ -78,13 +97,4 @@ def run(images_padded, dictionary, kernel_stride, padding_dims,
                             'f32')
   if name == 'bf16':
     raise NotImplementedError('convolutional inference has no bf16 fast mode')
-  vtc_hip.check(lib.vtc_conv_ista_fista(
-      vtc_hip.ptr(images_padded), vtc_hip.ptr(dictionary),
-      vtc_hip.ptr(initial_codes), vtc_hip.ptr(codes), ctypes.byref(geom),
-      float(stepsize), float(sparsity_weight), int(num_iters),
-      vtc_hip.variant_code(variant),
-      vtc_hip.threshold_mode(nonnegative_only, hard_threshold), eps,
-      vtc_hip.PRECISIONS[name], vtc_hip.ptr(ws), ws.numel(), ctypes.byref(iters_run),
-      vtc_hip.current_stream(device)), 'vtc_conv_ista_fista')
-  run.last_iters = iters_run.value
-  return codes
+  return name

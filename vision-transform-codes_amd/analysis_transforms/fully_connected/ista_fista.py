@@ -39,10 +39,15 @@ def run(images, dictionary, sparsity_weight, num_iters, variant='fista',
   precision : None | 'auto' | 'f32' | 'f16x3' | 'bf16x3' | 'bf16' -- extension,
       see vtc_hip.set_default_precision.  None uses the process-wide default.
       'f16x3' / 'bf16x3' run the fused persistent kernel when the shape allows
-      (n == 256, s in {256, 512, 1024}, no early stopping) and a tiled bf16
+      (n == 256, s in {256, 512, 1024}, no early stopping), the fused kernel
+      with streamed state for more atoms (multiples of 256), and the tiled
       hi/lo split contraction otherwise; 'bf16' exists only fused.
-      'auto' = 'f16x3' for the fused kernel's shapes, 'bf16x3' for other large
-      problems (b*s >= 2^22, n and s multiples of 4), 'f32' otherwise.
+      'auto' = 'f16x3' for the fused and the streamed kernels' shapes and for
+      other large problems (b*s*n >= 2.4e8, n and s multiples of 4), 'f32'
+      otherwise.  The choice depends on the shape alone: inputs that are views
+      at an address that is not 16-byte aligned (`patches[1:]` of 7x7
+      patches, a dictionary inside a larger buffer) are copied once, so every
+      legal tensor runs under every precision its shape allows.
   stepsize : float, optional -- extension: skip the Lipschitz eigen-solve and
       use this eta (tests inject the eta of a golden vector this way).
       Without it (and without early stopping) eta stays on the device, as the
@@ -65,6 +70,11 @@ def run(images, dictionary, sparsity_weight, num_iters, variant='fista',
     initial_codes = vtc_hip.require_device_tensor(
         initial_codes, 'initial_codes').contiguous()
     assert tuple(initial_codes.shape) == (b, s)
+  # read-only inputs: the fused and the split-tile routes want 16-byte
+  # aligned arrays (vtc_hip.aligned16)
+  images = vtc_hip.aligned16(images)
+  dictionary = vtc_hip.aligned16(dictionary)
+  initial_codes = vtc_hip.aligned16(initial_codes)
   if num_iters < 1:
     # the reference leaves `codes` unbound in this case
     raise UnboundLocalError(

@@ -37,7 +37,10 @@ def run(images, dictionary, group_assignments, sparsity_weight,
   if not ret_summed_gduplicates:
     raise NotImplementedError('TODO')
   lib = vtc_hip.load_library()
-  images = vtc_hip.require_device_tensor(images, 'images').contiguous()
+  # (aligned16: the streamed fused kernel wants 16-byte aligned patches; the
+  # grouped dictionary and codes below are fresh tensors)
+  images = vtc_hip.aligned16(
+      vtc_hip.require_device_tensor(images, 'images').contiguous())
   dictionary = vtc_hip.require_device_tensor(
       dictionary, 'dictionary').contiguous()
   b, n = images.shape

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "../../include/vtc_hip.h"
 
 namespace vtc {
@@ -31,6 +33,19 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 #define VTC_LAUNCH_CHECK() VTC_HIP_CHECK(hipGetLastError())
+
+// Name of the first pointer of the list that is not 16-byte aligned (a null
+// pointer is aligned), for the text of a refusal; "" when all are.
+struct NamedPointer {
+  const char* name;
+  const void* p;
+};
+static inline const char* first_unaligned16(
+    std::initializer_list<NamedPointer> list) {
+  for (const NamedPointer& e : list)
+    if (reinterpret_cast<uintptr_t>(e.p) & 15) return e.name;
+  return "";
+}
 
 static inline hipStream_t as_stream(void* s) {
   return reinterpret_cast<hipStream_t>(s);

@@ -1499,7 +1499,10 @@ template <int K>
 __global__ __launch_bounds__(256) void conv_grad_x3_kernel(
     const float* __restrict__ R, const float* __restrict__ C,
     float* __restrict__ slabs, ConvGeo g, int tiles_v, int tiles_u,
-    int64_t items) {
+    int64_t items, int wide) {
+  // wide: the 8 codes of a lane may be fetched as two 16-byte loads -- C is
+  // 16-byte aligned and the map width a multiple of 4, so that every image,
+  // map and row starts on a 16-byte boundary (cx_launch_grad_k); else dwords
   constexpr int NT = (K + 1) / 2;                  // accumulator tiles (2 dy each)
   constexpr int WROWS = kCxGradRows + 2 * NT;      // window rows incl. padding
   // The window operand of a lane starts at pixel 16 ks + 8 half + dx: a
@@ -1571,14 +1574,23 @@ __global__ __launch_bounds__(256) void conv_grad_x3_kernel(
           const unsigned off =
               atom_ok ? (unsigned)atom * map4 + (unsigned)(u * g.cw + v) * 4u
                       : 0x80000000u;
-          const cx_u32x4 lo4 =
-              __builtin_amdgcn_raw_buffer_load_b128(crs, off, 0, 0);
-          const cx_u32x4 hi4 =
-              __builtin_amdgcn_raw_buffer_load_b128(crs, off, 16, 0);
+          if (wide) {
+            const cx_u32x4 lo4 =
+                __builtin_amdgcn_raw_buffer_load_b128(crs, off, 0, 0);
+            const cx_u32x4 hi4 =
+                __builtin_amdgcn_raw_buffer_load_b128(crs, off, 16, 0);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            a[i] = (v + i < g.cw) ? __uint_as_float(lo4[i]) : 0.f;
-            a[4 + i] = (v + 4 + i < g.cw) ? __uint_as_float(hi4[i]) : 0.f;
+            for (int i = 0; i < 4; ++i) {
+              a[i] = (v + i < g.cw) ? __uint_as_float(lo4[i]) : 0.f;
+              a[4 + i] = (v + 4 + i < g.cw) ? __uint_as_float(hi4[i]) : 0.f;
+            }
+          } else {
+            // the same 8 floats, one dword each: a column past the row gets
+            // the out-of-range offset (reads as zero) like a missing atom
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+              a[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                  crs, (v + i < g.cw) ? off : 0x80000000u, 4u * i, 0));
           }
         }
         uint4 ah, al;
@@ -1991,10 +2003,15 @@ static int cx_launch_grad_k(const float* R, const float* C, float* slabs,
   const int tiles_v = (int)ceil_div(g.cw, kCxStrip);
   const int tiles_u = (int)ceil_div(g.ch, kCxGradRows);
   const int64_t items = (int64_t)tiles_v * tiles_u * g.b;
+  // 16-byte loads of the codes only where every one of them is 16-byte
+  // aligned: offset ((img * s + atom) * ch * cw + u * cw + v) * 4, v % 8 == 0
+  const int wide = (g.cw % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(C) & 15) == 0) ? 1 : 0;
   hipLaunchKernelGGL(conv_grad_x3_kernel<K>,
                      dim3((unsigned)cx_grad_blocks(g),
                           (unsigned)ceil_div(g.s, 128), (unsigned)g.c),
-                     dim3(256), 0, st, R, C, slabs, g, tiles_v, tiles_u, items);
+                     dim3(256), 0, st, R, C, slabs, g, tiles_v, tiles_u, items,
+                     wide);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }

@@ -116,6 +116,19 @@ static int run_generic(const float* images, const float* dictionary,
   const TiledIstaLayout L(ws, b, n, s);
   float* R = L.R;
   float* Dt = L.Dt;
+  if (x3 && (n % 4 != 0 || s % 4 != 0)) {
+    set_error("vtc_fc_ista_fista: bf16x3 outside the fused kernel needs n "
+              "and s to be multiples of 4");
+    return VTC_ERR_UNSUPPORTED;
+  }
+  // The split tiles read both operands 16 bytes at a time and their proximal
+  // epilogue moves the codes 16 bytes at a time (epi_prox.h), whatever wide_ok
+  // below says; Y, R, Dt and the out-of-place targets are workspace.  A
+  // dictionary or `codes` that is only 4-byte aligned runs the exact-f32
+  // tiles instead, whose loads and epilogue are gated per operand.
+  if (x3 && ((reinterpret_cast<uintptr_t>(dictionary) |
+              reinterpret_cast<uintptr_t>(codes)) & 15) != 0)
+    x3 = false;
   const int k1_slices = x3 ? gemm_x3_want_slices(b, n, s) : 1;
   double* delta_sum = L.delta_sum;
   unsigned* state = L.state;
@@ -141,9 +154,8 @@ static int run_generic(const float* images, const float* dictionary,
   float* Y = fista ? L.Y : codes;  // ISTA evaluates the gradient at the codes
   if (x3) {
     if (!gemm_x3_usable(Y, s, Dt, s) || !gemm_x3_usable(R, n, dictionary, n)) {
-      set_error("vtc_fc_ista_fista: bf16x3 outside the fused kernel needs n "
-                "and s to be multiples of 4 and 16-byte aligned operands");
-      return VTC_ERR_UNSUPPORTED;
+      set_error("vtc_fc_ista_fista: split tiles on an unaligned operand");
+      return VTC_ERR_INVALID_ARGUMENT;   // unreachable: gated above
     }
     int rc = launch_transpose(dictionary, Dt, s, n, st);
     if (rc != VTC_OK) return rc;
@@ -316,12 +328,24 @@ static int fc_ista_fista_impl(const float* images, const float* dictionary,
               "VTC_F16X3, VTC_BF16X3 or VTC_F32");
     return VTC_ERR_UNSUPPORTED;
   }
-  // (the register-resident kernels move patches and codes as float4)
+  // (the register-resident and the fused kernels move patches, dictionary
+  // rows and codes as float4: they run on 16-byte aligned pointers only, every
+  // other call takes the tiled route, which the workspace query covers)
   const bool aligned16 =
       ((reinterpret_cast<uintptr_t>(images) |
         reinterpret_cast<uintptr_t>(dictionary) |
         reinterpret_cast<uintptr_t>(codes) |
         reinterpret_cast<uintptr_t>(initial_codes)) & 15) == 0;
+  if (precision == VTC_BF16 && !aligned16) {
+    set_error("vtc_fc_ista_fista: VTC_BF16 exists only as the fused kernel, "
+              "which needs %s 16-byte aligned; use VTC_F16X3, VTC_BF16X3 or "
+              "VTC_F32",
+              first_unaligned16({{"images", images},
+                                 {"dictionary", dictionary},
+                                 {"initial_codes", initial_codes},
+                                 {"codes", codes}}));
+    return VTC_ERR_UNSUPPORTED;
+  }
   // 8x8 patches against 64 / 128 / 192 atoms, exact f32: everything on the CU
   if (precision == VTC_F32 && early_stopping_epsilon < 0.f && aligned16 &&
       num_iters <= fused_max_iters() && small_shape_supported(n, s))
@@ -335,14 +359,14 @@ static int fc_ista_fista_impl(const float* images, const float* dictionary,
                       stepsize, stepsize_dev, sparsity_weight, num_iters,
                       variant, threshold, workspace, workspace_bytes,
                       iters_run, st);
-  if (precision != VTC_F32 && fused_ok)
+  if (precision != VTC_F32 && fused_ok && aligned16)
     return run_fused(images, dictionary, initial_codes, codes, b, n, s,
                      stepsize, stepsize_dev, sparsity_weight, num_iters,
                      variant, threshold, precision, workspace, workspace_bytes,
                      iters_run, st);
   // 16x16 patches against more atoms than the on-chip state holds: the fused
   // kernel with streamed state
-  if (precision != VTC_F32 && precision != VTC_BF16 &&
+  if (precision != VTC_F32 && precision != VTC_BF16 && aligned16 &&
       early_stopping_epsilon < 0.f && num_iters <= fused_max_iters() &&
       stream_shape_supported(b, n, s, 1, precision))
     return run_stream(images, dictionary, initial_codes, codes, b, n, s, 1,

@@ -371,7 +371,14 @@ extern "C" int vtc_subspace_ista_fista(
   const int64_t slots = groups * m;
   // 16x16 patches, groups of 1/2/4/8 slots, no early stopping: the fused
   // persistent kernel with streamed state (fused_stream.hip)
-  if (precision != VTC_F32 && early_stopping_epsilon < 0.f &&
+  // (that kernel moves patches, dictionary rows and codes as float4: 16-byte
+  // aligned pointers only, the tiled route below serves the others)
+  const bool aligned16 =
+      ((reinterpret_cast<uintptr_t>(images) |
+        reinterpret_cast<uintptr_t>(grouped_dictionary) |
+        reinterpret_cast<uintptr_t>(grouped_codes) |
+        reinterpret_cast<uintptr_t>(initial_grouped)) & 15) == 0;
+  if (precision != VTC_F32 && early_stopping_epsilon < 0.f && aligned16 &&
       num_iters <= fused_max_iters_for_stream() &&
       stream_shape_supported(b, n, slots, m, precision))
     return run_stream(images, grouped_dictionary, initial_grouped,
@@ -384,6 +391,15 @@ extern "C" int vtc_subspace_ista_fista(
   // group shapes take the bf16 split
   bool f16 = (precision == VTC_F16X3);
   if (f16) precision = VTC_BF16X3;
+  if (precision == VTC_BF16X3 && (n % 4 != 0 || slots % 4 != 0)) {
+    set_error("vtc_subspace_ista_fista: bf16x3 needs n and G*m to be "
+              "multiples of 4");
+    return VTC_ERR_UNSUPPORTED;
+  }
+  // the split tiles read the dictionary rows 16 bytes at a time: a dictionary
+  // that is only 4-byte aligned runs the exact-f32 tiles, gated per operand
+  if (reinterpret_cast<uintptr_t>(grouped_dictionary) & 15)
+    precision = VTC_F32;
   if (!workspace || workspace_bytes < subspace_ws_bytes(b, n, slots)) {
     set_error("vtc_subspace_ista_fista: workspace too small");
     return VTC_ERR_WORKSPACE;
@@ -411,9 +427,9 @@ extern "C" int vtc_subspace_ista_fista(
   if (x3) {
     if (!gemm_x3_usable(Y, slots, DgT, slots) ||
         !gemm_x3_usable(R, n, grouped_dictionary, n)) {
-      set_error("vtc_subspace_ista_fista: bf16x3 needs n and G*m to be "
-                "multiples of 4 and 16-byte aligned operands");
-      return VTC_ERR_UNSUPPORTED;
+      set_error("vtc_subspace_ista_fista: split tiles on an unaligned "
+                "operand");
+      return VTC_ERR_INVALID_ARGUMENT;   // unreachable: gated above
     }
     int rc = launch_transpose(grouped_dictionary, DgT, slots, n, st);
     if (rc != VTC_OK) return rc;

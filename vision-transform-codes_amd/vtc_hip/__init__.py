@@ -218,6 +218,20 @@ def require_device_tensor(t, name, dtype=torch.float32):
   return t
 
 
+def aligned16(t):
+  """`t` itself when its data pointer is 16-byte aligned (always, for a tensor
+  that owns its storage), else a copy that is.  The C library takes any
+  element-aligned pointer (include/vtc_hip.h, Conventions) but keeps its
+  16-byte kernels -- the fused and the matrix-core routes -- for aligned
+  arrays; an inference plugin passes its read-only inputs through here so that
+  a view such as `patches[1:]` or a dictionary kept inside a larger buffer
+  still runs the route its shape selects.  Never used on a tensor a call
+  updates in place."""
+  if t is None or t.data_ptr() % 16 == 0:
+    return t
+  return t.clone(memory_format=torch.contiguous_format)
+
+
 def ptr(t):
   return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
