@@ -18,6 +18,7 @@
 // index i folds with period 2n, i mod 2n in [n, 2n) mirroring to 2n - 1 - i,
 // which stays right for windows wider than the image.
 #include "common.h"
+#include "sep_filter.h"
 
 #include <cmath>
 
@@ -35,13 +36,6 @@ struct Taps {
   int radius;
   double g[2 * kMaxRadius + 1];
 };
-
-__device__ __forceinline__ int fold(int i, int n) {
-  const int p = 2 * n;
-  int m = i % p;
-  if (m < 0) m += p;
-  return m < n ? m : p - 1 - m;
-}
 
 // float32 value the filter reads: the pixel (LLS) or its float32 square (LCN,
 // `image**2`).
@@ -149,12 +143,10 @@ __global__ void local_norm_rows_kernel(const float* __restrict__ x,
     const int64_t pix = e / c;
     const int px = (int)(pix % w);
     const int64_t row = pix - px;
-    double acc = 0.0;
-    for (int k = 0; k <= 2 * r; ++k) {
-      const int gx = fold(px + k - r, w);
-      acc += (double)filter_input(x[(row + gx) * c + ch], mode) * taps.g[k];
-    }
-    ws[e] = acc;
+    ws[e] = tap_sum(
+        [&](int k) { return taps.g[k]; }, 2 * r + 1, r, px, w, [&](int gx) {
+          return (double)filter_input(x[(row + gx) * c + ch], mode);
+        });
   }
 }
 
@@ -173,11 +165,9 @@ __global__ void local_norm_cols_kernel(const float* __restrict__ x,
     const int64_t prow = pix / w;
     const int py = (int)(prow % h);
     const int64_t plane = prow - py;
-    double acc = 0.0;
-    for (int k = 0; k <= 2 * r; ++k) {
-      const int gy = fold(py + k - r, h);
-      acc += ws[((plane + gy) * w + px) * c + ch] * taps.g[k];
-    }
+    const double acc = tap_sum(
+        [&](int k) { return taps.g[k]; }, 2 * r + 1, r, py, h,
+        [&](int gy) { return ws[((plane + gy) * w + px) * c + ch]; });
     epilogue(acc, x[e], mode, out + e, aux + e);
   }
 }

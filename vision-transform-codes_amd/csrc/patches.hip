@@ -14,11 +14,11 @@
 // and even, so the half-spectrum transform is exact).  hipFFT is opened with
 // dlopen at first use: the rest of the library has no dependency on it.
 #include "common.h"
+#include "fft_plans.h"
 
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstring>
-#include <hipfft/hipfft.h>
 
 #include <map>
 #include <mutex>
@@ -33,18 +33,7 @@ static unsigned flat_grid(int64_t total) {
   return (unsigned)blocks;
 }
 
-struct FftApi {
-  hipfftResult (*plan_many)(hipfftHandle*, int, int*, int*, int, int, int*,
-                            int, int, hipfftType, int);
-  hipfftResult (*exec_d2z)(hipfftHandle, hipfftDoubleReal*,
-                           hipfftDoubleComplex*);
-  hipfftResult (*exec_z2d)(hipfftHandle, hipfftDoubleComplex*,
-                           hipfftDoubleReal*);
-  hipfftResult (*set_stream)(hipfftHandle, hipStream_t);
-  bool ok;
-};
-
-static const FftApi& fft_api() {
+const FftApi& fft_api() {
   static FftApi api = [] {
     FftApi a{};
     // A process that imported PyTorch already holds PyTorch's own hipFFT
@@ -81,17 +70,13 @@ static const FftApi& fft_api() {
   return api;
 }
 
-struct FftPlans {
-  hipfftHandle forward, inverse;
-};
-
 // plans are cached per (device, h, w, batch)
-static int get_plans(int h, int w, int batch, FftPlans* out) {
+int get_plans(int h, int w, int batch, FftPlans* out) {
   static std::mutex lock;
   static std::map<std::tuple<int, int, int, int>, FftPlans> cache;
   const FftApi& api = fft_api();
   if (!api.ok) {
-    set_error("whitening: libhipfft.so could not be opened");
+    set_error("libhipfft.so could not be opened");
     return VTC_ERR_UNSUPPORTED;
   }
   int device = 0;
@@ -106,7 +91,7 @@ static int get_plans(int h, int w, int batch, FftPlans* out) {
                       HIPFFT_D2Z, batch) != HIPFFT_SUCCESS ||
         api.plan_many(&p.inverse, 2, n, nullptr, 1, 0, nullptr, 1, 0,
                       HIPFFT_Z2D, batch) != HIPFFT_SUCCESS) {
-      set_error("whitening: hipfftPlanMany failed for %dx%d x %d", h, w,
+      set_error("hipfftPlanMany failed for %dx%d x %d", h, w,
                 batch);
       return VTC_ERR_HIP;
     }

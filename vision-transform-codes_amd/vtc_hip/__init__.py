@@ -1,5 +1,6 @@
 """
-Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h).
+Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
+and include/vtc_image.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -150,6 +151,29 @@ SIGNATURES = {
     'vtc_row_center': (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp]),
 }
 
+IMAGE_ABI_VERSION = 1   # VTC_IMAGE_ABI_VERSION of include/vtc_image.h
+
+# The second header, include/vtc_image.h (same library): the image-level half
+# of utils/image_processing.py.  A table of its own, so that SIGNATURES stays
+# the surface of include/vtc_hip.h exactly.
+IMAGE_SIGNATURES = {
+    'vtc_image_abi_version': (_i32, []),
+    'vtc_img_filter_fd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32,
+                                                _i32]),
+    'vtc_img_filter_fd': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32,
+                                 _i32, _i32, _vp, _sz, _vp]),
+    'vtc_img_filter_sd_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32, _i32,
+                                                _i32, _i32]),
+    'vtc_img_filter_sd': (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32,
+                                 _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'vtc_img_tile_patches': (_i32, [_vp, _i32, _vp, _i64, _i32, _i32, _i32,
+                                    _i32, _i32, _vp]),
+    'vtc_img_assemble_patches': (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _i32,
+                                        _i32, _i32, _i32, _i32, _vp]),
+    'vtc_img_downsample': (_i32, [_vp, _i32, _vp, _i64, _i32, _i32, _i32,
+                                  _i32, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -166,12 +190,15 @@ def load_library():
         '(hipcc --offload-arch=gfx950).  There is no CPU fallback.'
         % (LIBRARY_PATH, _PKG_ROOT / 'csrc'))
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
-  for name, (restype, argtypes) in SIGNATURES.items():
-    fn = getattr(lib, name)   # AttributeError if the export is missing
-    fn.restype = restype
-    fn.argtypes = argtypes
+  for table in (SIGNATURES, IMAGE_SIGNATURES):
+    for name, (restype, argtypes) in table.items():
+      fn = getattr(lib, name)   # AttributeError if the export is missing
+      fn.restype = restype
+      fn.argtypes = argtypes
   if lib.vtc_abi_version() != ABI_VERSION:
     raise ImportError('libvtc_hip.so ABI version mismatch')
+  if lib.vtc_image_abi_version() != IMAGE_ABI_VERSION:
+    raise ImportError('libvtc_hip.so image ABI version mismatch')
   _lib = lib
   return lib
 
