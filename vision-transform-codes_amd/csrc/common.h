@@ -51,7 +51,9 @@ static inline hipStream_t as_stream(void* s) {
   return reinterpret_cast<hipStream_t>(s);
 }
 
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+__host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) {
+  return (a + b - 1) / b;
+}
 static inline size_t align_up(size_t v, size_t a) {
   return (v + a - 1) / a * a;
 }
@@ -105,6 +107,11 @@ static inline bool first_use_on_this_device(unsigned long long* seen) {
 }
 
 // ---- device helpers -----------------------------------------------------
+// Accumulator tile of a 32x32 MFMA, exact-f32 (gemm_f32.h) and split-operand
+// (split_operand.h) alike: lane l holds column l & 31, register r row
+// (r & 3) + 8 * (r >> 2) + 4 * (l >> 5).
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
 // The reference's elementwise arithmetic is un-fused f32 (one rounding per
 // torch op).  These wrappers keep hipcc from contracting a*b+c into an FMA.
 __device__ __forceinline__ float mul_rn(float a, float b) {
@@ -163,6 +170,16 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+// maximum of unsigned words: bit patterns of non-negative floats are ordered
+// like the floats, NaN on top
+__device__ __forceinline__ unsigned wave_max(unsigned v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)v, off, 64);
+    v = o > v ? o : v;
+  }
   return v;
 }
 

@@ -1,7 +1,6 @@
-// Unit-stride, single-channel convolutional ISTA/FISTA on the bf16 matrix pipe
-// with split operands ("bf16x3": hi = bf16(x), lo = bf16(x - hi), product
-// hi*hi + hi*lo + lo*hi accumulated in f32 -- float32-level accuracy, see
-// gemm_x3.h).  BASELINE configs[4]: 128 kernels of 11x11 on 256x256 images.
+// Unit-stride, single-channel convolutional ISTA/FISTA on the 16-bit matrix
+// pipe with split operands (float32-level accuracy, see split_operand.h).
+// BASELINE configs[4]: 128 kernels of 11x11 on 256x256 images.
 //
 // Restates analysis_transforms/convolutional/ista_fista.py:152-155 as two
 // contractions per iteration, neither with an im2col buffer in HBM:
@@ -31,12 +30,10 @@
 // written once per iteration.
 #pragma once
 
+#include "split_operand.h"
 #include "x3_scale.h"
 
 namespace vtc {
-
-typedef __bf16 cx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int cx_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kCxStrip = 64;       // code columns per wave unit (2 MFMA tiles)
 constexpr int kCxSynWaves = 8;
@@ -75,18 +72,10 @@ __host__ __device__ inline int cx_slot_tap(int m, int k) {
   return t < k * k ? t : -1;
 }
 
-__device__ __forceinline__ uint16_t cx_bits(__bf16 v) {
-  return __builtin_bit_cast(uint16_t, v);
-}
-
-// ------------------------------------------------ operand types and scales
-// Two 16-bit operand types behind one template flag.  F16 = false: bf16 hi/lo
-// (8 + 8 significand bits, 2^-17 per product: 1.6e-5 from the reference after
-// 200 iterations).  F16 = true: f16 hi/lo (11 + 11 bits, 2^-22 per product,
-// the float32 noise floor) at the same MFMA rate and the same bytes -- f16 has
-// 5 exponent bits, so every operand is brought to the range [16, 32) by a
-// power of two first (exact, and undone exactly on the f32 accumulators):
-//   * the kernels: one sigma_D per call (dictionary_scale_kernel);
+// ------------------------------------------------------------------ scales
+// The f16 split (F16 = true, split_operand.h) wants every operand brought to
+// the range [16, 32) by a power of two first:
+//   * the kernels: one sigma_D per call (cx_array_scale_kernel);
 //   * the residual: one sigma_R per launch, from max |R| which the kernel that
 //     WROTE the residual left in device memory (CxScales);
 //   * the momentum iterate Y as the synthesis operand: in the fused kernel one
@@ -94,36 +83,6 @@ __device__ __forceinline__ uint16_t cx_bits(__bf16 v) {
 //     the N index of the product, so its scale factors out of the sum over
 //     atoms); in the stand-alone synthesis kernel one sigma_Y per launch, from
 //     max |Y| left by the kernel that wrote Y.
-// An entry 2^12 below the maximum of its operand still has all 22 bits; below
-// that the lo part goes subnormal and the absolute error stays at 2^-29 of the
-// maximum.
-typedef _Float16 cx_f16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ f32x16 cx_mfma(const uint4& a, const uint4& b,
-                                          const f32x16& c) {
-  if (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(
-        __builtin_bit_cast(cx_f16x8, a), __builtin_bit_cast(cx_f16x8, b), c, 0,
-        0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-      __builtin_bit_cast(cx_bf16x8, a), __builtin_bit_cast(cx_bf16x8, b), c, 0,
-      0, 0);
-}
-
-// one value -> its 16-bit hi and lo parts (bit patterns)
-template <bool F16>
-__device__ __forceinline__ void cx_split1(float v, uint16_t& hi, uint16_t& lo) {
-  if (F16) {
-    const _Float16 h = (_Float16)v;
-    hi = __builtin_bit_cast(uint16_t, h);
-    lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
-  } else {
-    const __bf16 h = (__bf16)v;
-    hi = cx_bits(h);
-    lo = cx_bits((__bf16)(v - (float)h));
-  }
-}
 
 // ------------------------------------------------------------------ pack
 // syn image (uint16): [channel][atom chunk][plane][slot][s16 + 8]
@@ -177,40 +136,7 @@ __global__ void conv_x3_pack_kernel(const float* __restrict__ D,
       hi = ana + ((int64_t)chunk * channels + channel) * 2 * ana_plane + rem;
       lo = hi + ana_plane;
     }
-    cx_split1<F16>(v * sigma, *hi, *lo);
-  }
-}
-
-// registers (times a power-of-two scale) -> one MFMA operand pair
-template <bool F16>
-__device__ __forceinline__ void cx_split8(const float (&v)[8], float scale,
-                                          uint4& hi, uint4& lo) {
-  if (F16) {
-    // two values per conversion (v_cvt_pk_f16_f32, round to nearest even as the
-    // scalar one): the same arithmetic in fewer VALU instructions
-    typedef float pair_f32 __attribute__((ext_vector_type(2)));
-    typedef _Float16 pair_f16 __attribute__((ext_vector_type(2)));
-    unsigned hw[4], lw[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const pair_f32 x = {v[2 * j] * scale, v[2 * j + 1] * scale};
-      const pair_f16 h = __builtin_convertvector(x, pair_f16);
-      const pair_f16 l = __builtin_convertvector(
-          x - __builtin_convertvector(h, pair_f32), pair_f16);
-      hw[j] = __builtin_bit_cast(unsigned, h);
-      lw[j] = __builtin_bit_cast(unsigned, l);
-    }
-    hi = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-    lo = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-  } else {
-    cx_bf16x8 h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      h[j] = (__bf16)v[j];
-      l[j] = (__bf16)(v[j] - (float)h[j]);
-    }
-    hi = __builtin_bit_cast(uint4, h);
-    lo = __builtin_bit_cast(uint4, l);
+    split1<F16>(v * sigma, *hi, *lo);
   }
 }
 
@@ -351,7 +277,7 @@ __global__ __launch_bounds__(512) void conv_synth_x3_kernel(
       uint4 bh[NI], bl[NI];
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        cx_split8<F16>(src[ni][kk], y_scale, bh[ni], bl[ni]);
+        split_packed<F16, 8>(src[ni][kk], y_scale, bh[ni], bl[ni]);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const int off = (32 * mt + l31) * pitch + ks * 16 + 8 * half;
@@ -359,9 +285,9 @@ __global__ __launch_bounds__(512) void conv_synth_x3_kernel(
         const uint4 al = *reinterpret_cast<const uint4*>(Dl + off);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-          acc[mt][ni] = cx_mfma<F16>(ah, bh[ni], acc[mt][ni]);
-          acc[mt][ni] = cx_mfma<F16>(ah, bl[ni], acc[mt][ni]);
-          acc[mt][ni] = cx_mfma<F16>(al, bh[ni], acc[mt][ni]);
+          acc[mt][ni] = mfma16<F16>(ah, bh[ni], acc[mt][ni]);
+          acc[mt][ni] = mfma16<F16>(ah, bl[ni], acc[mt][ni]);
+          acc[mt][ni] = mfma16<F16>(al, bh[ni], acc[mt][ni]);
         }
       }
     }
@@ -547,7 +473,7 @@ __global__ __launch_bounds__(256) void conv_analysis_x3_kernel(
         const float v =
             (y < g.H && x < g.W) ? Rimg[(int64_t)y * g.W + x] : 0.f;
         uint16_t hb, lb;
-        cx_split1<F16>(F16 ? v * r_scale : v, hb, lb);
+        split1<F16>(F16 ? v * r_scale : v, hb, lb);
         if (SHIFT > 1) {
           // pixel x of a row sits at position x - c of copy c; the first c
           // pixels of the window land in the padding of the copy before
@@ -701,9 +627,9 @@ __global__ __launch_bounds__(256) void conv_analysis_x3_kernel(
         const uint4 al = *reinterpret_cast<const uint4*>(Dl + off);
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          acc[ma][ni] = cx_mfma<F16>(ah, bh[ni], acc[ma][ni]);
-          acc[ma][ni] = cx_mfma<F16>(ah, bl[ni], acc[ma][ni]);
-          acc[ma][ni] = cx_mfma<F16>(al, bh[ni], acc[ma][ni]);
+          acc[ma][ni] = mfma16<F16>(ah, bh[ni], acc[ma][ni]);
+          acc[ma][ni] = mfma16<F16>(ah, bl[ni], acc[ma][ni]);
+          acc[ma][ni] = mfma16<F16>(al, bh[ni], acc[ma][ni]);
         }
       }
     }
@@ -828,7 +754,7 @@ __global__ void conv_x3_pack_synp_kernel(const float* __restrict__ D,
       if (atom < s) v = D[(int64_t)atom * taps + t];
     }
     uint16_t* hi = synp + (int64_t)chunk * 2 * plane + rem;
-    cx_split1<F16>(v * sigma, hi[0], hi[plane]);
+    split1<F16>(v * sigma, hi[0], hi[plane]);
   }
 }
 
@@ -981,7 +907,7 @@ __global__ __launch_bounds__(512) void conv_fused_x3_kernel(
       const int e = tid + 512 * q;
       if (e < F::WIN_ELEMS) {
         uint16_t hb, lb;
-        cx_split1<F16>(F16 ? wreg[q] * r_scale : wreg[q], hb, lb);
+        split1<F16>(F16 ? wreg[q] * r_scale : wreg[q], hb, lb);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           // pixel x of a row sits at position x - c of copy c.  The first c
@@ -1031,9 +957,9 @@ __global__ __launch_bounds__(512) void conv_fused_x3_kernel(
     const unsigned blk = block_of(it, ma);
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4) {
-      const cx_u32x4 y4 = __builtin_amdgcn_raw_buffer_load_b128(
+      const u32x4 y4 = __builtin_amdgcn_raw_buffer_load_b128(
           ors, lane16 + 1024u * k4, blk, 0);
-      const cx_u32x4 c4 = __builtin_amdgcn_raw_buffer_load_b128(
+      const u32x4 c4 = __builtin_amdgcn_raw_buffer_load_b128(
           crs, lane16 + 1024u * k4, blk, 0);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1122,7 +1048,7 @@ __global__ __launch_bounds__(512) void conv_fused_x3_kernel(
     const unsigned blk = block_of(it, ma);
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4) {
-      cx_u32x4 c4;
+      u32x4 c4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) c4[j] = __float_as_uint(cv[4 * k4 + j]);
       // block offset in the vector offset, scalar offset 0: with a register
@@ -1142,7 +1068,7 @@ __global__ __launch_bounds__(512) void conv_fused_x3_kernel(
 #pragma unroll
       for (int j = 0; j < 8; ++j) v8[j] = yn[8 * ks + j];
       uint4 bh, bl;
-      cx_split8<F16>(v8, col_scale, bh, bl);
+      split_packed<F16, 8>(v8, col_scale, bh, bl);
       const int base = l31 * F::SYN_PITCH + 32 * ma + 16 * ks + 8 * half;
       uint4 ah = *reinterpret_cast<const uint4*>(Sh + base);
       uint4 al = *reinterpret_cast<const uint4*>(Sl + base);
@@ -1155,9 +1081,9 @@ __global__ __launch_bounds__(512) void conv_fused_x3_kernel(
           al_n = *reinterpret_cast<const uint4*>(Sl + off);
         }
         __builtin_amdgcn_sched_barrier(0);           // keep the reads up here
-        Q[mt] = cx_mfma<F16>(ah, bh, Q[mt]);
-        Q[mt] = cx_mfma<F16>(ah, bl, Q[mt]);
-        Q[mt] = cx_mfma<F16>(al, bh, Q[mt]);
+        Q[mt] = mfma16<F16>(ah, bh, Q[mt]);
+        Q[mt] = mfma16<F16>(ah, bl, Q[mt]);
+        Q[mt] = mfma16<F16>(al, bh, Q[mt]);
         __builtin_amdgcn_sched_barrier(0);
         ah = ah_n;
         al = al_n;
@@ -1261,12 +1187,12 @@ __global__ __launch_bounds__(512) void conv_fused_x3_kernel(
         AnaOps nx = ops;
         if (dy + 1 < K) nx = ana_load(Wb, dy + 1);
         __builtin_amdgcn_sched_barrier(0);           // keep the reads up here
-        acc[0] = cx_mfma<F16>(ops.ah0, ops.bh, acc[0]);
-        acc[1] = cx_mfma<F16>(ops.ah1, ops.bh, acc[1]);
-        acc[0] = cx_mfma<F16>(ops.ah0, ops.bl, acc[0]);
-        acc[1] = cx_mfma<F16>(ops.ah1, ops.bl, acc[1]);
-        acc[0] = cx_mfma<F16>(ops.al0, ops.bh, acc[0]);
-        acc[1] = cx_mfma<F16>(ops.al1, ops.bh, acc[1]);
+        acc[0] = mfma16<F16>(ops.ah0, ops.bh, acc[0]);
+        acc[1] = mfma16<F16>(ops.ah1, ops.bh, acc[1]);
+        acc[0] = mfma16<F16>(ops.ah0, ops.bl, acc[0]);
+        acc[1] = mfma16<F16>(ops.ah1, ops.bl, acc[1]);
+        acc[0] = mfma16<F16>(ops.al0, ops.bh, acc[0]);
+        acc[1] = mfma16<F16>(ops.al1, ops.bh, acc[1]);
         __builtin_amdgcn_sched_barrier(0);
         ops = nx;
       }
@@ -1546,9 +1472,8 @@ __global__ __launch_bounds__(256) void conv_grad_x3_kernel(
         const int ry = e / kCxAnaPitch, rx = e % kCxAnaPitch;
         const int y = u0 + ry, x = v0 + rx;
         const float v = (y < g.H && x < g.W) ? Rimg[(int64_t)y * g.W + x] : 0.f;
-        const __bf16 h = (__bf16)v;
-        const uint16_t hb = cx_bits(h);
-        const uint16_t lb = cx_bits((__bf16)(v - (float)h));
+        uint16_t hb, lb;
+        split1<false>(v, hb, lb);
         // pixel x of a row sits at position x - c of copy c; the first c
         // pixels of a row land on the last positions of the row (or plane)
         // before, which no read reaches (reads end at position 78 of 88)
@@ -1575,9 +1500,9 @@ __global__ __launch_bounds__(256) void conv_grad_x3_kernel(
               atom_ok ? (unsigned)atom * map4 + (unsigned)(u * g.cw + v) * 4u
                       : 0x80000000u;
           if (wide) {
-            const cx_u32x4 lo4 =
+            const u32x4 lo4 =
                 __builtin_amdgcn_raw_buffer_load_b128(crs, off, 0, 0);
-            const cx_u32x4 hi4 =
+            const u32x4 hi4 =
                 __builtin_amdgcn_raw_buffer_load_b128(crs, off, 16, 0);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1594,7 +1519,7 @@ __global__ __launch_bounds__(256) void conv_grad_x3_kernel(
           }
         }
         uint4 ah, al;
-        cx_split8<false>(a, 1.f, ah, al);
+        split_packed<false, 8>(a, ah, al);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
           const uint16_t* bp = Wc + 8 + (dx & 3) * COPY +
@@ -1606,9 +1531,9 @@ __global__ __launch_bounds__(256) void conv_grad_x3_kernel(
           const uint2 l1 = *reinterpret_cast<const uint2*>(bp + PLANE + 4);
           const uint4 bh = make_uint4(h0.x, h0.y, h1.x, h1.y);
           const uint4 bl = make_uint4(l0.x, l0.y, l1.x, l1.y);
-          acc[nt] = cx_mfma<false>(ah, bh, acc[nt]);
-          acc[nt] = cx_mfma<false>(ah, bl, acc[nt]);
-          acc[nt] = cx_mfma<false>(al, bh, acc[nt]);
+          acc[nt] = mfma16<false>(ah, bh, acc[nt]);
+          acc[nt] = mfma16<false>(ah, bl, acc[nt]);
+          acc[nt] = mfma16<false>(al, bh, acc[nt]);
         }
       }
     }

@@ -103,9 +103,9 @@ struct EpiGroupProx {
     const unsigned ld4 = (unsigned)(ld * 4);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const x3_u32x4 y4 = __builtin_amdgcn_raw_buffer_load_b128(
+      const u32x4 y4 = __builtin_amdgcn_raw_buffer_load_b128(
           ctx.yrs, off, (unsigned)(8 * q) * ld4, 0);
-      const x3_u32x4 c4 = __builtin_amdgcn_raw_buffer_load_b128(
+      const u32x4 c4 = __builtin_amdgcn_raw_buffer_load_b128(
           ctx.crs, off, (unsigned)(8 * q) * ld4, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -162,7 +162,7 @@ struct EpiGroupProx {
           total = add_rn(total, __shfl_xor(total, o, 64));
         sq[0] = sq[1] = sq[2] = sq[3] = total;
       }
-      x3_u32x4 y4, c4;
+      u32x4 y4, c4;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float cn;

@@ -74,8 +74,6 @@ struct FusedParams {
   unsigned long long* stamps;  // diagnostic build only: 8 cycle sums
 };
 
-#define VTC_MFMA(a, b, c) mfma_frag<F16>(a, b, c)
-
 // LDS plan (bytes), NPH phases, NP precision parts, CREG phases of C in VGPRs:
 //   Cst : (NPH-CREG) x 16 KiB   previous codes, [phase][wave][group][lane] f32x4
 //   Yx  : 2 x NP x 8704         Y' exchange, double buffered,
@@ -158,10 +156,10 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
   const int cst_ln = w * 4096 + lane * 16;          // + pl*16384 + g*1024
 
   // ---- per-wave state --------------------------------------------------
-  f32x16v Y[NPH];    // gradient evaluation point, this wave's tile per phase
-  f32x16v Cr[CR];    // previous codes of the first CREG phases
-  f32x16v Xr[2];     // the patches, this wave's two 32-pixel blocks
-  f32x16v Racc[2];
+  f32x16 Y[NPH];    // gradient evaluation point, this wave's tile per phase
+  f32x16 Cr[CR];    // previous codes of the first CREG phases
+  f32x16 Xr[2];     // the patches, this wave's two 32-pixel blocks
+  f32x16 Racc[2];
   uint4 ring[NP][RING];
 
   // element e of a 32x32 accumulator: row (e&3) + 8(e>>2) + 4h, column r
@@ -285,12 +283,12 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
     for (int e = 0; e < 16; ++e) Racc[nb][e] = 0.f;
 
   // write the wave's tile of Y (as bf16 parts) into exchange buffer `buf`
-  auto publish_y = [&](const f32x16v& y, int buf) {
+  auto publish_y = [&](const f32x16& y, int buf) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float v4[4] = {y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3]};
       uint2 hi, lo;
-      split4<F16, NP>(v4, &hi, &lo);
+      split_packed<F16, 4, NP == 2>(v4, hi, lo);
       char* dst = Yx + buf * NP * kYxPart + yx_wr + 16 * g;
       *reinterpret_cast<uint2*>(dst) = hi;
       if (NP == 2) *reinterpret_cast<uint2*>(dst + kYxPart) = lo;
@@ -352,10 +350,10 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
 #pragma unroll
         for (int part = 0; part < NP; ++part)
           a[part] = pipe ? ring[part][i % RING] : VTC_LOAD_T(part, p, nb, ks);
-        Racc[nb] = VTC_MFMA(a[0], yb[0], Racc[nb]);
+        Racc[nb] = mfma16<F16>(a[0], yb[0], Racc[nb]);
         if constexpr (NP == 2) {
-          Racc[nb] = VTC_MFMA(a[0], yb[1], Racc[nb]);
-          Racc[nb] = VTC_MFMA(a[1], yb[0], Racc[nb]);
+          Racc[nb] = mfma16<F16>(a[0], yb[1], Racc[nb]);
+          Racc[nb] = mfma16<F16>(a[1], yb[0], Racc[nb]);
         }
         // (epilogue arithmetic of another phase, if any, before the refill:
         // see step 1)
@@ -442,7 +440,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
         const float v4[4] = {v[nb][4 * g], v[nb][4 * g + 1], v[nb][4 * g + 2],
                              v[nb][4 * g + 3]};
         uint2 hi, lo;
-        split4<F16, NP>(v4, &hi, &lo);
+        split_packed<F16, 4, NP == 2>(v4, hi, lo);
         char* dst = Rx + rx_wr + 64 * nb + 16 * g;
         *reinterpret_cast<uint2*>(dst) = hi;
         if (NP == 2) *reinterpret_cast<uint2*>(dst + kRxPart) = lo;
@@ -484,14 +482,14 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
   }
   if (STAMP) t0 = stamp_now();
 
-  f32x16v Gb[2];     // gradient tiles of two consecutive phases
+  f32x16 Gb[2];     // gradient tiles of two consecutive phases
   float4 cold4;      // previous codes of the 4 elements being processed
   float cn4[4];
 
   // Proximal step + extrapolation for element e of phase p
   // (ista_fista.py:105-131); elements are visited in order 0..15, group
   // loads/stores of C and the bf16 publication of Y' happen at group edges.
-  auto epilogue_elem = [&](int p, int e, const f32x16v& Gp, float beta) {
+  auto epilogue_elem = [&](int p, int e, const f32x16& Gp, float beta) {
     const int g = e >> 2, k = e & 3;
     if (MODE == 7) {         // diagnostic: step 1 with (almost) no epilogue work
       const float cn = Y[p][e] + Gp[e];
@@ -540,7 +538,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
       const float v4[4] = {Y[p][4 * g], Y[p][4 * g + 1], Y[p][4 * g + 2],
                            Y[p][4 * g + 3]};
       uint2 hi, lo;
-      split4<F16, NP>(v4, &hi, &lo);
+      split_packed<F16, 4, NP == 2>(v4, hi, lo);
       char* dst = Yx + (p & 1) * NP * kYxPart + yx_wr + 16 * g;
       *reinterpret_cast<uint2*>(dst) = hi;
       if (NP == 2) *reinterpret_cast<uint2*>(dst + kYxPart) = lo;
@@ -550,7 +548,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
   // step 1 of phase p (stream segment sg): Gb[p&1] = D[tile] R_k, with the
   // epilogue of phase p-1 interleaved element by element when `overlap`
   auto step1 = [&](int p, int sg, bool overlap, float beta) {
-    f32x16v& G = Gb[p & 1];
+    f32x16& G = Gb[p & 1];
 #pragma unroll
     for (int e = 0; e < 16; ++e) G[e] = 0.f;
     uint4 rb_next[NP];
@@ -568,10 +566,10 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
           rb_next[part] = *reinterpret_cast<const uint4*>(
               Rx + part * kRxPart + rx_rd + 32 * (i + 1));
       }
-      G = VTC_MFMA(ring[0][i % RING], rb[0], G);
+      G = mfma16<F16>(ring[0][i % RING], rb[0], G);
       if constexpr (NP == 2) {
-        G = VTC_MFMA(ring[0][i % RING], rb[1], G);
-        G = VTC_MFMA(ring[1][i % RING], rb[0], G);
+        G = mfma16<F16>(ring[0][i % RING], rb[1], G);
+        G = mfma16<F16>(ring[1][i % RING], rb[0], G);
       }
       // epilogue arithmetic first, then the refill: a wave blocks at a
       // buffer load while the vector-memory path is busy, and in that order

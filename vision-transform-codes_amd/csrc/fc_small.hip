@@ -19,8 +19,6 @@
 
 namespace vtc {
 
-typedef float sm_f32x16 __attribute__((ext_vector_type(16)));
-
 bool small_shape_supported(int64_t n, int64_t s) {
   // (256 atoms: 336 live accumulator-layout registers plus the working set do
   // not allocate without spills; that shape stays on the tiled path)
@@ -73,8 +71,8 @@ __global__ __launch_bounds__(256) void fc_small_kernel(SmallParams P) {
     const bool valid = p < P.b;
     // this lane's patch, in the row order of the accumulator tiles
     constexpr bool kKeepX = true;
-    sm_f32x16 X[2], Y[ST], C[ST];
-    auto load_patch = [&](sm_f32x16 (&dst)[2]) {
+    f32x16 X[2], Y[ST], C[ST];
+    auto load_patch = [&](f32x16 (&dst)[2]) {
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(256) void fc_small_kernel(SmallParams P) {
       int lane_off = l31;
       if (ST > 4) asm volatile("" : "+v"(lane_off));
       // R^T = D^T Y^T - X^T
-      sm_f32x16 R0, R1;
+      f32x16 R0, R1;
       if (!kKeepX) load_patch(X);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(256) void fc_small_kernel(SmallParams P) {
       // G^T = D R^T per atom tile, gradient step, threshold, extrapolation
 #pragma unroll
       for (int t = 0; t < ST; ++t) {
-        sm_f32x16 G;
+        f32x16 G;
 #pragma unroll
         for (int r = 0; r < 16; ++r) G[r] = 0.f;
 #pragma unroll

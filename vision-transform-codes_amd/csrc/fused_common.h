@@ -1,20 +1,12 @@
 // Device helpers shared by the fused persistent kernels (fc_fused.hip: state on
-// chip; fused_stream.hip: state streamed): fragment types, the hi/lo operand
-// split, the MFMA wrapper, dictionary packing into MFMA fragment order.
+// chip; fused_stream.hip: state streamed): dictionary packing into MFMA
+// fragment order, the f16 dictionary scale, buffer loads, stamps.  The hi/lo
+// operand split and the MFMA wrapper are split_operand.h's.
 #pragma once
 #include "common.h"
+#include "split_operand.h"
 
 namespace vtc {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
-
-__host__ __device__ static inline int64_t ceil_div_dev(int64_t a, int64_t b) {
-  return (a + b - 1) / b;
-}
 
 constexpr int kFP = 32;    // patches per workgroup
 constexpr int kFN = 256;   // pixels per patch
@@ -26,23 +18,12 @@ constexpr int kPhaseAtoms = 128;
 // packT fragment (phase p, pixel block nb of 32, k-step ks over the phase's
 // atoms), lane l:
 //   D[128p + 16ks + 8(l>>5) + j][32nb + (l&31)]
-// LO = 0 stores bf16(x), LO = 1 stores bf16(x - float(bf16(x))).
-template <bool F16>
-__device__ __forceinline__ unsigned short split_part(float x, int lo) {
-  if (F16) {
-    const _Float16 hi = (_Float16)x;
-    const _Float16 r = lo ? (_Float16)(x - (float)hi) : hi;
-    return __builtin_bit_cast(unsigned short, r);
-  }
-  const __bf16 hi = (__bf16)x;
-  const __bf16 r = lo ? (__bf16)(x - (float)hi) : hi;
-  return __builtin_bit_cast(unsigned short, r);
-}
 
 // F16: sigma_D = 2^(8 - floor(log2 max|D|)), so that max |sigma_D D| lies in
 // [256, 512): far from the f16 overflow (65504) and with the lo parts of all
 // but vanishing entries in the normal range.  One block; scale[0] = sigma_D,
-// scale[1] = 1 / sigma_D.
+// scale[1] = 1 / sigma_D.  (Not cx_array_scale_kernel of x3_scale.h: that one
+// aims at [16, 32) and works on bit patterns; this range is the fused kernels'.)
 static __global__ __launch_bounds__(1024) void dictionary_scale_kernel(
     const float* __restrict__ D, int64_t count, float* __restrict__ scale) {
   __shared__ float part[16];
@@ -121,60 +102,6 @@ __device__ __forceinline__ float shrink_fast(float c, float cutoff) {
   }
   return shrink(c, cutoff, MODE);
 }
-
-__device__ __forceinline__ bf16x8 as_frag(const uint4& u) {
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-__device__ __forceinline__ f16x8 as_frag16(const uint4& u) {
-  return __builtin_bit_cast(f16x8, u);
-}
-template <bool F16>
-__device__ __forceinline__ f32x16v mfma_frag(const uint4& a, const uint4& b,
-                                             const f32x16v& c) {
-  if (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag16(a), as_frag16(b),
-                                                  c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a), as_frag(b), c, 0,
-                                                 0, 0);
-}
-
-// four f32 values -> their 16-bit hi parts and (NP == 2) lo parts, packed
-template <bool F16, int NP>
-__device__ __forceinline__ void split4(const float (&v)[4], uint2* hi_out,
-                                       uint2* lo_out) {
-  if (F16) {
-    // two values per instruction (v_cvt_pk_f16_f32, round to nearest even as
-    // the scalar conversion; v_pk_add_f32): the same arithmetic in fewer VALU
-    // instructions
-    typedef float pair_f32 __attribute__((ext_vector_type(2)));
-    typedef _Float16 pair_f16 __attribute__((ext_vector_type(2)));
-    unsigned hw[2], lw[2] = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const pair_f32 x = {v[2 * k], v[2 * k + 1]};
-      const pair_f16 h = __builtin_convertvector(x, pair_f16);
-      hw[k] = __builtin_bit_cast(unsigned, h);
-      if (NP == 2)
-        lw[k] = __builtin_bit_cast(
-            unsigned, __builtin_convertvector(
-                          x - __builtin_convertvector(h, pair_f32), pair_f16));
-    }
-    *hi_out = make_uint2(hw[0], hw[1]);
-    if (NP == 2) *lo_out = make_uint2(lw[0], lw[1]);
-  } else {
-    bf16x4 hi, lo;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      hi[k] = (__bf16)v[k];
-      if (NP == 2) lo[k] = (__bf16)(v[k] - (float)hi[k]);
-    }
-    *hi_out = __builtin_bit_cast(uint2, hi);
-    if (NP == 2) *lo_out = __builtin_bit_cast(uint2, lo);
-  }
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint4 buffer_load16(__amdgpu_buffer_rsrc_t rsrc,
                                                unsigned voff, unsigned soff) {

@@ -78,7 +78,7 @@ __global__ void stream_state_pack_kernel(const float* __restrict__ rows,
                                          float4* __restrict__ frag0,
                                          float4* __restrict__ frag1,
                                          int64_t b, int nph) {
-  const int64_t total = (ceil_div_dev(b, 32)) * nph * 1024;
+  const int64_t total = ceil_div(b, 32) * nph * 1024;
   const int64_t slots = (int64_t)nph * 128;
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < total;
        u += (int64_t)gridDim.x * blockDim.x) {
@@ -102,7 +102,7 @@ __global__ void stream_state_unpack_kernel(const float4* __restrict__ frag,
                                            const float* __restrict__ scale,
                                            float* __restrict__ rows, int64_t b,
                                            int nph) {
-  const int64_t total = (ceil_div_dev(b, 32)) * nph * 1024;
+  const int64_t total = ceil_div(b, 32) * nph * 1024;
   const int64_t slots = (int64_t)nph * 128;
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < total;
        u += (int64_t)gridDim.x * blockDim.x) {
@@ -128,8 +128,6 @@ __device__ __forceinline__ float add_across_halves(float x) {
   const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return add_rn(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
 }
-
-#define VTC_MFMA(a, b, c) mfma_frag<F16>(a, b, c)
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -324,7 +322,7 @@ __global__ __launch_bounds__(512) void fused_stream_kernel(StreamParams P) {
   const int rx_wr = r * kSRxRow + 128 * w + 8 * h;
   const int slot_ln = w * 4096 + lane * 16;      // + slot, + 16384 (c_{k-1}), + g*1024
 
-  f32x16v Racc[2], Gb[2];
+  f32x16 Racc[2], Gb[2];
   uint4 ring[NP][RING];
   const float* x_row =
       P.images + (live ? patch : 0) * kFN + 64 * w + 4 * h;   // + 32 nb + 8 g
@@ -411,7 +409,7 @@ __global__ __launch_bounds__(512) void fused_stream_kernel(StreamParams P) {
   // publish four values of y' for step 3
   auto publish4 = [&](const float (&v4)[4], int buf, int g) {
     uint2 hi, lo;
-    split4<F16, NP>(v4, &hi, &lo);
+    split_packed<F16, 4, NP == 2>(v4, hi, lo);
     char* dst = Yx + buf * NP * kSYxPart + yx_wr + 16 * g;
     *reinterpret_cast<uint2*>(dst) = hi;
     *reinterpret_cast<uint2*>(dst + kSYxPart) = lo;
@@ -446,9 +444,9 @@ __global__ __launch_bounds__(512) void fused_stream_kernel(StreamParams P) {
           a[part] = pipe ? ring[part][i % RING]
                          : buffer_load16(rs[part], frag_voff,
                                          cur + VTC_OFF_T(i));
-        Racc[nb] = VTC_MFMA(a[0], yb[0], Racc[nb]);
-        Racc[nb] = VTC_MFMA(a[0], yb[1], Racc[nb]);
-        Racc[nb] = VTC_MFMA(a[1], yb[0], Racc[nb]);
+        Racc[nb] = mfma16<F16>(a[0], yb[0], Racc[nb]);
+        Racc[nb] = mfma16<F16>(a[0], yb[1], Racc[nb]);
+        Racc[nb] = mfma16<F16>(a[1], yb[0], Racc[nb]);
         if (pipe) {
           const int j = i + RING;
           const unsigned off =
@@ -528,7 +526,7 @@ __global__ __launch_bounds__(512) void fused_stream_kernel(StreamParams P) {
         const float v4[4] = {v[nb][4 * g], v[nb][4 * g + 1], v[nb][4 * g + 2],
                              v[nb][4 * g + 3]};
         uint2 hi, lo;
-        split4<F16, NP>(v4, &hi, &lo);
+        split_packed<F16, 4, NP == 2>(v4, hi, lo);
         char* dst = Rx + rx_wr + 64 * nb + 16 * g;
         *reinterpret_cast<uint2*>(dst) = hi;
         *reinterpret_cast<uint2*>(dst + kSRxPart) = lo;
@@ -656,7 +654,7 @@ __global__ __launch_bounds__(512) void fused_stream_kernel(StreamParams P) {
                    float beta_prev, float beta) {
     const unsigned cur = seg_base(0, q);
     const unsigned nxt = seg_base(nk, nq);
-    f32x16v& G = Gb[set];
+    f32x16& G = Gb[set];
 #pragma unroll
     for (int e = 0; e < 16; ++e) G[e] = 0.f;
     uint4 rb_next[NP];
@@ -674,9 +672,9 @@ __global__ __launch_bounds__(512) void fused_stream_kernel(StreamParams P) {
           rb_next[part] = *reinterpret_cast<const uint4*>(
               Rx + part * kSRxPart + rx_rd + 32 * (i + 1));
       }
-      G = VTC_MFMA(ring[0][i % RING], rb[0], G);
-      G = VTC_MFMA(ring[0][i % RING], rb[1], G);
-      G = VTC_MFMA(ring[1][i % RING], rb[0], G);
+      G = mfma16<F16>(ring[0][i % RING], rb[0], G);
+      G = mfma16<F16>(ring[0][i % RING], rb[1], G);
+      G = mfma16<F16>(ring[1][i % RING], rb[0], G);
       if (overlap) {
         epilogue_elem(q - 1, set ^ 1, i, beta_prev, beta);
         __builtin_amdgcn_sched_barrier(0);

@@ -3,8 +3,8 @@
 // v_mfma_f32_32x32x2_f32 takes f32 operands and accumulates in f32: per output
 // element the result is a k-ordered fmaf chain, i.e. the same arithmetic class
 // as the reference's torch.mm in float32.  This is the "parity" contraction
-// every plugin can fall back to for any shape; the bf16 kernels in
-// fc_fista_fused.hip are the fast path for the headline shape.
+// every plugin can fall back to for any shape; the split-operand kernels in
+// fc_fused.hip are the fast path for the headline shape.
 //
 // Block = 256 threads = 4 waves in a 2x2 arrangement, block tile 128x128,
 // wave tile 64x64 (2x2 MFMA tiles, 64 accumulator VGPRs), K step 16.
@@ -14,13 +14,11 @@
 #pragma once
 
 #include "common.h"
-#include "x3_scale.h"
+#include "x3_scale.h"   // EpiMinusMax leaves max |C| in a slot
 
 #include <type_traits>
 
 namespace vtc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kGemmBM = 128;
 constexpr int kGemmBN = 128;
@@ -76,13 +74,6 @@ template <class E, bool = epi_elem_fetch<E>::value>
 struct epi_fetched { struct type {}; };
 template <class E>
 struct epi_fetched<E, true> { typedef typename E::Fetched type; };
-
-typedef __bf16 x3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x3_bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int x3_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kX3BM = 128, kX3BN = 128, kX3BK = 32;
-constexpr int kX3TileBytes = 128 * 64;   // one operand part: 128 rows x 64 B
 
 // C[M,N] = opA * opB over k in [z*k_chunk, min(K, (z+1)*k_chunk)), z=blockIdx.y
 //   A_KC: A is stored [M][K] (k contiguous, leading dim lda); else [K][M].

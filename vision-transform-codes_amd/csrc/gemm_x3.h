@@ -1,15 +1,11 @@
-// Tiled contraction with float32-level accuracy on the bf16 matrix pipe
-// ("bf16x3"), for shapes the fused FISTA kernel does not cover.
+// Tiled contraction with float32-level accuracy on the 16-bit matrix pipe
+// (split operands, split_operand.h), for shapes the fused FISTA kernel does
+// not cover.
 //
 //   C[M,N] = A[M,K] * B[N,K]^T         A, B float32 in HBM, k contiguous
 //
-// While a tile is staged into LDS every f32 value is split into
-//   hi = bf16(x),  lo = bf16(x - float(hi))
-// and the product is formed as hi*hi + hi*lo + lo*hi with
-// v_mfma_f32_32x32x16_bf16, f32 accumulate: relative error ~2^-16 per product
-// (measured end to end: same as the reference's own f32 noise after 200 FISTA
-// iterations) at 3 MFMA per algorithmic product, i.e. 5.3x the peak of the
-// exact-f32 MFMA used by gemm_f32.h.
+// Every f32 value is split into its hi and lo parts while a tile is staged
+// into LDS.
 //
 // Block = 4 waves (2x2), block tile 128x128, wave tile 64x64 (2x2 MFMA tiles),
 // K step 32.  LDS rows are 64 B (32 bf16); the 16-byte chunk index is XORed
@@ -19,9 +15,13 @@
 
 #include "common.h"
 #include "gemm_f32.h"
+#include "split_operand.h"
 #include "x3_scale.h"
 
 namespace vtc {
+
+constexpr int kX3BM = 128, kX3BN = 128, kX3BK = 32;
+constexpr int kX3TileBytes = 128 * 64;   // one operand part: 128 rows x 64 B
 
 struct GemmX3Args {
   const float* A;
@@ -39,55 +39,6 @@ struct GemmX3Args {
   const unsigned* a_max = nullptr;
   unsigned* clear = nullptr;
 };
-
-typedef _Float16 x3_f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 x3_f16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ f32x16 x3_mfma(const uint4& a, const uint4& b,
-                                          const f32x16& c) {
-  if (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(
-        __builtin_bit_cast(x3_f16x8, a), __builtin_bit_cast(x3_f16x8, b), c, 0,
-        0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-      __builtin_bit_cast(x3_bf16x8, a), __builtin_bit_cast(x3_bf16x8, b), c, 0,
-      0, 0);
-}
-
-// four values (times a power-of-two scale) -> packed hi and lo parts
-template <bool F16>
-__device__ __forceinline__ void x3_split4(const float (&v)[4], float scale,
-                                          uint2* hi_out, uint2* lo_out) {
-  if (F16) {
-    // two values per instruction: v_pk_mul_f32, v_cvt_pk_f16_f32 (round to
-    // nearest even, as the scalar conversion), v_pk_add_f32 -- 3 VALU
-    // instructions per element instead of 5; the same arithmetic
-    typedef float pair_f32 __attribute__((ext_vector_type(2)));
-    typedef _Float16 pair_f16 __attribute__((ext_vector_type(2)));
-    unsigned hw[2], lw[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const pair_f32 x = {v[2 * k] * scale, v[2 * k + 1] * scale};
-      const pair_f16 h = __builtin_convertvector(x, pair_f16);
-      const pair_f16 l = __builtin_convertvector(
-          x - __builtin_convertvector(h, pair_f32), pair_f16);
-      hw[k] = __builtin_bit_cast(unsigned, h);
-      lw[k] = __builtin_bit_cast(unsigned, l);
-    }
-    *hi_out = make_uint2(hw[0], hw[1]);
-    *lo_out = make_uint2(lw[0], lw[1]);
-  } else {
-    x3_bf16x4 hi, lo;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      hi[k] = (__bf16)v[k];
-      lo[k] = (__bf16)(v[k] - (float)hi[k]);
-    }
-    *hi_out = __builtin_bit_cast(uint2, hi);
-    *lo_out = __builtin_bit_cast(uint2, lo);
-  }
-}
 
 // operand scales of a launch: A, B, and the factor that undoes both
 template <bool F16>
@@ -146,7 +97,7 @@ __device__ __forceinline__ void x3_stage_store(char* hi_base, char* lo_base,
     const int line = f >> 3, kq = f & 7;
     const float v[4] = {regs[i].x, regs[i].y, regs[i].z, regs[i].w};
     uint2 hi, lo;
-    x3_split4<F16>(v, scale, &hi, &lo);
+    split_packed<F16, 4>(v, scale, hi, lo);
     const int off = x3_lds_off(line, kq >> 1) + 8 * (kq & 1);
     *reinterpret_cast<uint2*>(hi_base + off) = hi;
     *reinterpret_cast<uint2*>(lo_base + off) = lo;
@@ -245,9 +196,9 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmX3Args g, Epi epi) {
       for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          acc[mi][ni] = x3_mfma<F16>(ah[mi], bh[ni], acc[mi][ni]);
-          acc[mi][ni] = x3_mfma<F16>(ah[mi], bl[ni], acc[mi][ni]);
-          acc[mi][ni] = x3_mfma<F16>(al[mi], bh[ni], acc[mi][ni]);
+          acc[mi][ni] = mfma16<F16>(ah[mi], bh[ni], acc[mi][ni]);
+          acc[mi][ni] = mfma16<F16>(ah[mi], bl[ni], acc[mi][ni]);
+          acc[mi][ni] = mfma16<F16>(al[mi], bh[ni], acc[mi][ni]);
         }
       }
     }
@@ -363,7 +314,7 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel8(GemmX3Args g, Epi epi) {
   const __amdgpu_buffer_rsrc_t ars = tile_rsrc(g.A, g.lda, m0, g.M);
   const __amdgpu_buffer_rsrc_t brs = tile_rsrc(g.B, g.ldb, n0, g.N);
   auto stage_load = [&](const __amdgpu_buffer_rsrc_t& rs, int64_t ld,
-                        int64_t k0, x3_u32x4 (&regs)[2]) {
+                        int64_t k0, u32x4 (&regs)[2]) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int f = tid + i * 512;
@@ -375,7 +326,7 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel8(GemmX3Args g, Epi epi) {
     }
   };
   auto stage_store = [&](char* hi_base, char* lo_base,
-                         const x3_u32x4 (&regs)[2], float scale) {
+                         const u32x4 (&regs)[2], float scale) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int f = tid + i * 512;
@@ -385,7 +336,7 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel8(GemmX3Args g, Epi epi) {
                           __uint_as_float(regs[i][2]),
                           __uint_as_float(regs[i][3])};
       uint2 hi, lo;
-      x3_split4<F16>(v, scale, &hi, &lo);
+      split_packed<F16, 4>(v, scale, hi, lo);
       const int off = x3_lds_off(line, kq >> 1) + 8 * (kq & 1);
       *reinterpret_cast<uint2*>(hi_base + off) = hi;
       *reinterpret_cast<uint2*>(lo_base + off) = lo;
@@ -411,16 +362,16 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel8(GemmX3Args g, Epi epi) {
       }
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        acc[ni] = x3_mfma<F16>(ah, bh[ni], acc[ni]);
-        acc[ni] = x3_mfma<F16>(ah, bl[ni], acc[ni]);
-        acc[ni] = x3_mfma<F16>(al, bh[ni], acc[ni]);
+        acc[ni] = mfma16<F16>(ah, bh[ni], acc[ni]);
+        acc[ni] = mfma16<F16>(ah, bl[ni], acc[ni]);
+        acc[ni] = mfma16<F16>(al, bh[ni], acc[ni]);
       }
     }
   };
   auto k_of = [&](int kt) { return k_begin + (int64_t)kt * kX3BK; };
 
   // two register stages: loads of step kt+2 are issued during step kt
-  x3_u32x4 a0[2], b0[2], a1[2], b1[2];
+  u32x4 a0[2], b0[2], a1[2], b1[2];
   stage_load(ars, g.lda, k_of(0), a0);
   stage_load(brs, g.ldb, k_of(0), b0);
   stage_store(lds[0][0], lds[0][1], a0, a_scale);

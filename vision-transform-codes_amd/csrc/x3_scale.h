@@ -1,10 +1,9 @@
-// Power-of-two operand scales of the f16 hi/lo split ("f16x3") outside the
-// fused fully-connected kernels: f16 has 5 exponent bits, so an operand is
-// brought to the range [16, 32) by a power of two before it is split (exact,
-// and undone exactly on the f32 accumulators).  Static operands (dictionaries)
+// Power-of-two operand scales of the f16 hi/lo split (split_operand.h) outside
+// the fused fully-connected kernels: an operand is brought to the range
+// [16, 32) before it is split.  Static operands (dictionaries)
 // get one scale per call; an operand that a kernel wrote in the previous launch
 // gets its scale from max |x|, which that kernel left in device memory.
-// Shared by conv_x3.h and gemm_x3.h.
+// Shared by conv_x3.h, gemm_x3.h and the max-tracking epilogues.
 #pragma once
 
 #include "common.h"
@@ -43,23 +42,27 @@ __device__ __forceinline__ void cx_raise_word(unsigned* word, unsigned v) {
     atomicMax(word, v);
 }
 
-// block-wide maximum of m (>= 0) into ONE word; `red` = 16 words of LDS nobody
-// else uses around this call (the barriers are inside)
-__device__ __forceinline__ void cx_publish_max_word(float m, unsigned* word,
-                                                    unsigned* red) {
-  unsigned v = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, off, 64);
-    v = o > v ? o : v;
-  }
-  const int wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
+// Block-wide maximum of m (>= 0): thread 0 folds the waves' maxima and hands
+// the bit pattern to `use`.  `red` = 16 words of LDS nobody else uses around
+// this call (the barrier is inside); WAVES = waves of the block where the
+// kernel fixes them, 0: from blockDim.
+template <int WAVES = 0, class Use>
+__device__ __forceinline__ void cx_block_max(float m, unsigned* red, Use use) {
+  unsigned v = wave_max(__float_as_uint(m));
+  const int wave = threadIdx.x >> 6;
+  const int waves = WAVES ? WAVES : (int)((blockDim.x + 63) >> 6);
   if ((threadIdx.x & 63) == 0) red[wave] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < waves; ++w) v = red[w] > v ? red[w] : v;
-    cx_raise_word(word, v);
+    use(v);
   }
+}
+
+// block-wide maximum of m (>= 0) into ONE word (`red`: see cx_block_max)
+__device__ __forceinline__ void cx_publish_max_word(float m, unsigned* word,
+                                                    unsigned* red) {
+  cx_block_max(m, red, [&](unsigned v) { cx_raise_word(word, v); });
 }
 
 // the first block of a launch clears `count` words
@@ -80,7 +83,8 @@ __device__ __forceinline__ void cx_scale_of_bits(unsigned bits, float* s,
   *inv = usable ? __uint_as_float((unsigned)(254 - field) << 23) : 1.f;
 }
 
-// every lane of the calling wave gets the maximum over the slot's words
+// every lane of the calling wave gets the maximum over the slot's words (32
+// of them: a tree over 32 lanes, not wave_max)
 __device__ __forceinline__ unsigned cx_read_max(const unsigned* slot) {
   const int lane = threadIdx.x & 63;
   unsigned v = slot ? slot[(lane & (kCxMaxWords - 1)) * kCxMaxStride] : 0u;
@@ -92,23 +96,12 @@ __device__ __forceinline__ unsigned cx_read_max(const unsigned* slot) {
   return v;
 }
 
-// block-wide maximum of m (>= 0) added to the slot; `red` = 16 words of LDS
-// nobody else uses around this call (the barriers are inside)
+// block-wide maximum of m (>= 0) added to the slot (`red`: see cx_block_max)
 __device__ __forceinline__ void cx_publish_max(float m, unsigned* slot,
                                                unsigned* red) {
-  unsigned v = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, off, 64);
-    v = o > v ? o : v;
-  }
-  const int wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < waves; ++w) v = red[w] > v ? red[w] : v;
+  cx_block_max(m, red, [&](unsigned v) {
     cx_raise_word(slot + (blockIdx.x & (kCxMaxWords - 1)) * kCxMaxStride, v);
-  }
+  });
 }
 
 __device__ __forceinline__ void cx_clear_slot(unsigned* slot) {
@@ -116,24 +109,15 @@ __device__ __forceinline__ void cx_clear_slot(unsigned* slot) {
     slot[threadIdx.x * kCxMaxStride] = 0u;
 }
 
-// {sigma, 1 / sigma} of a small array (the kernels): one block
+// {sigma, 1 / sigma} of a small array (the kernels): one block.  (The fused FC
+// kernels' dictionary_scale_kernel, fused_common.h, aims at [256, 512).)
 static __global__ __launch_bounds__(1024) void cx_array_scale_kernel(
     const float* __restrict__ x, int64_t count, float* __restrict__ scale) {
   __shared__ unsigned red[16];
   float m = 0.f;
   for (int64_t i = threadIdx.x; i < count; i += 1024) m = fmaxf(m, fabsf(x[i]));
-  unsigned v = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, off, 64);
-    v = o > v ? o : v;
-  }
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 16; ++w) v = red[w] > v ? red[w] : v;
-    cx_scale_of_bits(v, scale, scale + 1);
-  }
+  cx_block_max<16>(m, red,
+                   [&](unsigned v) { cx_scale_of_bits(v, scale, scale + 1); });
 }
 
 // max |x| of a large array into a CxScales slot (warm start: the initial
@@ -164,12 +148,7 @@ static __global__ __launch_bounds__(256) void cx_image_max_kernel(
 // wave-level form for epilogue functors (no LDS, no barrier): one atomic per
 // wave
 __device__ __forceinline__ void cx_publish_max_wave(float m, unsigned* slot) {
-  unsigned v = __float_as_uint(m);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, off, 64);
-    v = o > v ? o : v;
-  }
+  const unsigned v = wave_max(__float_as_uint(m));
   if ((threadIdx.x & 63) == 0)
     cx_raise_word(slot + ((blockIdx.x + (threadIdx.x >> 6)) &
                           (kCxMaxWords - 1)) * kCxMaxStride, v);
