@@ -61,6 +61,21 @@
  *     is an inference call with early_stopping_epsilon >= 0, which has to read
  *     one flag back per iteration exactly like the reference's
  *     `stop_early = (avg < eps)` does (ista_fista.py:143-144).
+ *   - streams: EVERY device operation of a call -- kernels, memsets, copies,
+ *     the hipFFT transforms -- is issued on `stream`, none on the null stream
+ *     or on a stream of the library's own, so a call is ordered after what the
+ *     caller put on `stream` before it and before what the caller puts there
+ *     afterwards, and needs no other synchronisation.  Calls on different
+ *     streams of one device may be in flight together, provided they share no
+ *     output and no workspace (shared inputs are fine: no call writes one).
+ *     The library keeps two things per process on a device: the vtc_init()
+ *     table, which is read-only after it is placed, and the hipFFT plans of
+ *     vtc_whiten_center_surround / vtc_img_filter_fd, which are kept per
+ *     (device, stream, shape) and bound to their stream when they are made:
+ *     two streams never execute through one plan or share the work area
+ *     hipFFT may have allocated inside it.  Plans live until the process ends;
+ *     a stream handle that is destroyed and later handed out again finds the
+ *     plans of its predecessor, bound to the same handle.
  *   - no allocation inside: scratch comes from the caller as `workspace`, sized
  *     by the matching *_workspace_bytes() query.  The per-device constants of
  *     the library (the 64 KiB FISTA momentum table) are placed by vtc_init().

@@ -26,10 +26,15 @@
  *     and writes the caller's arrays element by element; no entry point
  *     refuses a pointer for its alignment.  `workspace` must be 256-byte
  *     aligned.
- *   - functions only enqueue work on `stream` and return.
+ *   - functions only enqueue work on `stream` and return.  Every device
+ *     operation of a call is issued on `stream`; calls on different streams of
+ *     one device may be in flight together, provided they share no output and
+ *     no workspace (vtc_hip.h, Conventions, "streams").
  *   - no allocation inside: scratch comes from the caller as `workspace`,
- *     sized by the matching *_workspace_bytes() query.  (hipFFT plans are
- *     created once per call shape and kept.)
+ *     sized by the matching *_workspace_bytes() query.  The hipFFT plans of
+ *     vtc_img_filter_fd are the only per-process device state here: one pair
+ *     per (device, stream, call shape), made at the first such call, bound to
+ *     that stream then and kept, so that two streams never share a plan.
  *   - return value: VTC_OK or a VTC_ERR_* code of vtc_hip.h; vtc_last_error()
  *     gives text.  Null pointers, bad sizes and unsupported shapes are
  *     answered before any device work.

@@ -21,6 +21,10 @@ is NOT 16-byte aligned: the flat buffer grows by `skew` bytes, the leading
 guard with it, and both guards still touch the payload's first and last byte.
 tests/test_pointer_alignment_gpu.py runs the fence table on such payloads.
 
+`fenced_staged(value, device)` is an arena whose payload is left poisoned, with
+the value beside it in pinned host memory: tests/test_stream_order_gpu.py
+uploads it on a side stream, behind a delay.
+
 The module runs on the CPU as well (`self_test`), which is how the suite shows
 that the fences bite without a GPU and without touching product code.
 """
@@ -130,6 +134,20 @@ def fenced_copy(value, device, skew=0):
   return f.payload, f
 
 
+def fenced_staged(value, device):
+  """(payload, fence, pinned): a fenced arena shaped like `value` whose payload
+  still holds the 0xFF poison, and `value` in pinned host memory, for a caller
+  that uploads it later on a stream of its own choice
+  (tests/test_stream_order_gpu.py)."""
+  if not torch.is_tensor(value):
+    value = torch.from_numpy(np.ascontiguousarray(value))
+  f = Fence(value.shape, value.dtype, device)
+  pinned = value.contiguous()
+  if f.flat.is_cuda:
+    pinned = pinned.pin_memory()
+  return f.payload, f, pinned
+
+
 def fenced_workspace(nbytes, device, skew=0):
   """Scratch of exactly `nbytes` bytes (not rounded up), 0xFF-filled."""
   return fenced((int(nbytes),), torch.uint8, device, skew=skew)
@@ -175,6 +193,13 @@ def self_test(device='cpu'):
     reports.append(str(e))
   else:
     raise AssertionError('fence missed an unwritten element')
+
+  value = np.arange(35, dtype=np.float32).reshape(5, 7)
+  payload, fence, pinned = fenced_staged(value, device)
+  fence.assert_untouched('staged arena before its upload')
+  fence.assert_intact('staged arena')
+  payload.copy_(pinned)
+  assert np.array_equal(payload.cpu().numpy(), value)
 
   ws, fence = fenced_workspace(1000, device)
   assert ws.numel() == 1000 and fence.guard % GUARD_QUANTUM == 0

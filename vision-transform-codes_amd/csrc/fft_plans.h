@@ -25,7 +25,8 @@ struct FftPlans {
   hipfftHandle forward, inverse;
 };
 
-// plans are cached per (device, h, w, batch)
-int get_plans(int h, int w, int batch, FftPlans* out);
+// plans are cached per (device, stream, h, w, batch) and bound to `st` when
+// they are made: execute through them on that stream only
+int get_plans(hipStream_t st, int h, int w, int batch, FftPlans* out);
 
 }  // namespace vtc

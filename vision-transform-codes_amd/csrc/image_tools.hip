@@ -432,11 +432,11 @@ extern "C" int vtc_img_filter_fd(const void* images, int dtype,
     return VTC_ERR_WORKSPACE;
   }
   const int64_t planes = count * c;
+  hipStream_t st = as_stream(stream);
   FftPlans plans;
-  int rc = get_plans(fh, fw, (int)planes, &plans);
+  int rc = get_plans(st, fh, fw, (int)planes, &plans);
   if (rc != VTC_OK) return rc;
   const FftApi& api = fft_api();
-  hipStream_t st = as_stream(stream);
   Carver ws(workspace);
   const FilterFdLayout L(ws, planes, fh, fw);
   const unsigned grid = grid_for(planes * fh * fw);
@@ -449,9 +449,7 @@ extern "C" int vtc_img_filter_fd(const void* images, int dtype,
                        0, st, static_cast<const uint8_t*>(images), L.real,
                        count, h, w, c, fh, fw);
   VTC_LAUNCH_CHECK();
-  if (api.set_stream(plans.forward, st) != HIPFFT_SUCCESS ||
-      api.set_stream(plans.inverse, st) != HIPFFT_SUCCESS ||
-      api.exec_d2z(plans.forward, L.real, L.spec) != HIPFFT_SUCCESS) {
+  if (api.exec_d2z(plans.forward, L.real, L.spec) != HIPFFT_SUCCESS) {
     set_error("%s: forward transform failed", who);
     return VTC_ERR_HIP;
   }

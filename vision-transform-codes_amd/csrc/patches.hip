@@ -70,10 +70,13 @@ const FftApi& fft_api() {
   return api;
 }
 
-// plans are cached per (device, h, w, batch)
-int get_plans(int h, int w, int batch, FftPlans* out) {
+// plans are cached per (device, stream, h, w, batch) and bound to their
+// stream once, here, under the lock: a plan owns whatever work area hipFFT
+// allocated for it, so two streams never execute through the same handle, and
+// no call rebinds a handle another host thread may be executing through
+int get_plans(hipStream_t st, int h, int w, int batch, FftPlans* out) {
   static std::mutex lock;
-  static std::map<std::tuple<int, int, int, int>, FftPlans> cache;
+  static std::map<std::tuple<int, hipStream_t, int, int, int>, FftPlans> cache;
   const FftApi& api = fft_api();
   if (!api.ok) {
     set_error("libhipfft.so could not be opened");
@@ -82,7 +85,7 @@ int get_plans(int h, int w, int batch, FftPlans* out) {
   int device = 0;
   VTC_HIP_CHECK(hipGetDevice(&device));
   std::lock_guard<std::mutex> guard(lock);
-  const auto key = std::make_tuple(device, h, w, batch);
+  const auto key = std::make_tuple(device, st, h, w, batch);
   auto it = cache.find(key);
   if (it == cache.end()) {
     FftPlans p;
@@ -93,6 +96,11 @@ int get_plans(int h, int w, int batch, FftPlans* out) {
                       HIPFFT_Z2D, batch) != HIPFFT_SUCCESS) {
       set_error("hipfftPlanMany failed for %dx%d x %d", h, w,
                 batch);
+      return VTC_ERR_HIP;
+    }
+    if (api.set_stream(p.forward, st) != HIPFFT_SUCCESS ||
+        api.set_stream(p.inverse, st) != HIPFFT_SUCCESS) {
+      set_error("hipfftSetStream failed for %dx%d x %d", h, w, batch);
       return VTC_ERR_HIP;
     }
     it = cache.emplace(key, p).first;
@@ -317,11 +325,11 @@ extern "C" int vtc_whiten_center_surround(const float* images, float* out,
     return VTC_ERR_WORKSPACE;
   }
   const int64_t planes = count * c;
+  hipStream_t st = as_stream(stream);
   FftPlans plans;
-  int rc = get_plans(h, w, (int)planes, &plans);
+  int rc = get_plans(st, h, w, (int)planes, &plans);
   if (rc != VTC_OK) return rc;
   const FftApi& api = fft_api();
-  hipStream_t st = as_stream(stream);
   Carver ws(workspace);
   const WhitenLayout L(ws, planes, h, w, norm_and_threshold != 0);
   double* real = L.real;
@@ -338,9 +346,7 @@ extern "C" int vtc_whiten_center_surround(const float* images, float* out,
                      dim3(flat_grid(planes * h * w)), dim3(256), 0, st, images,
                      real, count, h, w, c);
   VTC_LAUNCH_CHECK();
-  if (api.set_stream(plans.forward, st) != HIPFFT_SUCCESS ||
-      api.set_stream(plans.inverse, st) != HIPFFT_SUCCESS ||
-      api.exec_d2z(plans.forward, real, L.spec) != HIPFFT_SUCCESS) {
+  if (api.exec_d2z(plans.forward, real, L.spec) != HIPFFT_SUCCESS) {
     set_error("vtc_whiten_center_surround: forward transform failed");
     return VTC_ERR_HIP;
   }
