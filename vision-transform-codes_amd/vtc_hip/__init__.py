@@ -1,6 +1,6 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
-and include/vtc_image.h).
+include/vtc_image.h and include/vtc_codec.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -174,6 +174,23 @@ IMAGE_SIGNATURES = {
                                   _i32, _vp]),
 }
 
+CODEC_ABI_VERSION = 1   # VTC_CODEC_ABI_VERSION of include/vtc_codec.h
+
+# The third header, include/vtc_codec.h (same library): the JPEG source coding
+# of utils/jpeg.py.  Again a table of its own.
+CODEC_SIGNATURES = {
+    'vtc_codec_abi_version': (_i32, []),
+    'vtc_jpeg_quantize': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    'vtc_jpeg_dequantize': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    'vtc_jpeg_symbol_counts': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'vtc_jpeg_stream_bits': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    'vtc_jpeg_bit_offsets_workspace_bytes': (_sz, [_i64]),
+    'vtc_jpeg_bit_offsets': (_i32, [_vp, _i64, _vp, _vp, _sz, _vp]),
+    'vtc_jpeg_pack': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _sz, _vp, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -190,7 +207,7 @@ def load_library():
         '(hipcc --offload-arch=gfx950).  There is no CPU fallback.'
         % (LIBRARY_PATH, _PKG_ROOT / 'csrc'))
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
-  for table in (SIGNATURES, IMAGE_SIGNATURES):
+  for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -199,6 +216,8 @@ def load_library():
     raise ImportError('libvtc_hip.so ABI version mismatch')
   if lib.vtc_image_abi_version() != IMAGE_ABI_VERSION:
     raise ImportError('libvtc_hip.so image ABI version mismatch')
+  if lib.vtc_codec_abi_version() != CODEC_ABI_VERSION:
+    raise ImportError('libvtc_hip.so codec ABI version mismatch')
   _lib = lib
   return lib
 
