@@ -1,0 +1,400 @@
+// Decoder of the packed JPEG streams (include/vtc_decode.h): packed bits back
+// to levels.  DESIGN.md 4.12 states the rules and why the shape is this one.
+//
+// Decoding is serial inside a row -- where a codeword starts is known only
+// once the one before it has been read -- and parallel across rows.  So one
+// LANE owns one row: 64 consecutive rows per wave, 256 per block.  (The
+// packer's shape, one wave per row, would leave 63 lanes idle here.)  The
+// streams of neighbouring rows are adjacent in memory, so the byte loads of a
+// wave fall in one short range.  Lanes diverge on the number of tokens of
+// their rows; that is inherent.
+//
+// Three steps per call, all on the caller's stream:
+//   1. levels is zero-filled (rows are sparse: a lane stores its nonzero
+//      levels only, a dense row write would be s * 4 bytes apart across lanes)
+//   2. decode_tables_kernel, one block: left-aligns the at most 272 codewords
+//      to 64 bits, sorts each table, checks neighbours for prefix or equality
+//      and builds a first-level lookup of kLutBits bits per table, into the
+//      caller's workspace
+//   3. unpack_kernel: the tables go to LDS, every lane walks its row
+//
+// A codeword of at most kLutBits bits is found by one LDS read; a longer one
+// by predecessor search in the sorted array: for a prefix-free code the match
+// is the largest left-aligned codeword <= the window, provided the window
+// really starts with it.
+#include <limits.h>
+
+#include "../../include/vtc_decode.h"
+#include "common.h"
+
+namespace vtc {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kAcSymbols = 256, kDcSymbols = 16;
+constexpr int kSymbols = kAcSymbols + kDcSymbols;   // AC bytes, DC categories
+constexpr int kDcBase = kAcSymbols;
+constexpr int kEob = 0x00, kZrl = 0xF0;
+constexpr int kLutBits = 10;
+constexpr int kLutSize = 1 << kLutBits;
+constexpr int kMaxCodeBits = 64;
+
+typedef unsigned long long u64;
+
+// meta word of a codeword: length << 9 | symbol id (ids below 272, lengths
+// 1..64); 0 is no codeword.
+__host__ __device__ constexpr unsigned meta_of(int len, int id) {
+  return (unsigned)len << 9 | (unsigned)id;
+}
+
+struct DecodeLayout {
+  u64* code;        // [272] left-aligned, sorted: AC from 0, DC from 256
+  uint16_t* meta;   // [272] meta words of the sorted codewords
+  uint16_t* lut;    // [2][1024] meta word of the codeword a prefix starts with
+  int32_t* head;    // [4] AC count, DC count, 1 + bad symbol id or 0, unused
+  explicit DecodeLayout(Carver& c) {
+    code = c.take<u64>(kSymbols);
+    meta = c.take<uint16_t>(kSymbols);
+    lut = c.take<uint16_t>(2 * kLutSize);
+    head = c.take<int32_t>(4);
+  }
+};
+
+// ---- table preparation ------------------------------------------------------
+// (key, length, id) order; entries of length 0 are not compared at all.
+__device__ __forceinline__ bool sorts_before(u64 ka, int la, int ia, u64 kb,
+                                             int lb, int ib) {
+  if (ka != kb) return ka < kb;
+  if (la != lb) return la < lb;
+  return ia < ib;
+}
+
+__global__ __launch_bounds__(kBlock) void decode_tables_kernel(
+    const u64* __restrict__ ac_code, const uint8_t* __restrict__ ac_len,
+    const u64* __restrict__ dc_code, const uint8_t* __restrict__ dc_len,
+    DecodeLayout ws, u64* __restrict__ status) {
+  __shared__ u64 key[kSymbols], sorted_key[kSymbols];
+  __shared__ uint8_t len[kSymbols];
+  __shared__ uint16_t sorted_meta[kSymbols];
+  __shared__ uint16_t lut[2 * kLutSize];
+  __shared__ int count[2], bad;
+  const int tid = threadIdx.x;
+  if (tid < 2) count[tid] = 0;
+  if (tid == 0) bad = INT_MAX;
+  for (int i = tid; i < kSymbols; i += kBlock) {
+    int l = i < kDcBase ? ac_len[i] : dc_len[i - kDcBase];
+    if (l > kMaxCodeBits) l = kMaxCodeBits;
+    const u64 c = i < kDcBase ? ac_code[i] : dc_code[i - kDcBase];
+    len[i] = (uint8_t)l;
+    key[i] = l ? c << (kMaxCodeBits - l) : 0;   // bits above `l` fall off
+    sorted_key[i] = 0;
+    sorted_meta[i] = 0;
+  }
+  for (int i = tid; i < 2 * kLutSize; i += kBlock) lut[i] = 0;
+  __syncthreads();
+
+  // rank sort, each table on its own
+  for (int i = tid; i < kSymbols; i += kBlock) {
+    if (!len[i]) continue;
+    const int table = i >= kDcBase;
+    const int base = table ? kDcBase : 0;
+    const int n = table ? kDcSymbols : kAcSymbols;
+    int rank = 0;
+    for (int j = base; j < base + n; ++j)
+      if (len[j] && sorts_before(key[j], len[j], j, key[i], len[i], i)) ++rank;
+    sorted_key[base + rank] = key[i];
+    sorted_meta[base + rank] = (uint16_t)meta_of(len[i], i);
+    atomicAdd(&count[table], 1);
+  }
+  __syncthreads();
+
+  // If a codeword is a prefix of any other, it is one of its successor in
+  // sorted order: neighbours suffice.
+  for (int i = tid; i < kSymbols; i += kBlock) {
+    const int table = i >= kDcBase;
+    const int r = i - (table ? kDcBase : 0);
+    if (r + 1 >= count[table]) continue;
+    const u64 a = sorted_key[i], b = sorted_key[i + 1];
+    const int la = sorted_meta[i] >> 9, lb = sorted_meta[i + 1] >> 9;
+    if (la <= lb && ((a ^ b) >> (kMaxCodeBits - la)) == 0) {
+      atomicMin(&bad, (int)(sorted_meta[i] & 511));
+      if (la == lb) atomicMin(&bad, (int)(sorted_meta[i + 1] & 511));
+    }
+  }
+  __syncthreads();
+
+  // first level: every kLutBits-bit prefix that starts with a short codeword.
+  // The code is prefix-free here, so the ranges of two codewords are disjoint.
+  if (bad == INT_MAX) {
+    for (int i = tid; i < kSymbols; i += kBlock) {
+      const int table = i >= kDcBase;
+      const int r = i - (table ? kDcBase : 0);
+      if (r >= count[table]) continue;
+      const int l = sorted_meta[i] >> 9;
+      if (l > kLutBits) continue;
+      const int first = (int)(sorted_key[i] >> (kMaxCodeBits - kLutBits));
+      const int span = 1 << (kLutBits - l);
+      for (int q = 0; q < span; ++q)   // first + span <= kLutSize
+        lut[table * kLutSize + first + q] = sorted_meta[i];
+    }
+  }
+  __syncthreads();
+
+  for (int i = tid; i < kSymbols; i += kBlock) {
+    ws.code[i] = sorted_key[i];
+    ws.meta[i] = sorted_meta[i];
+  }
+  for (int i = tid; i < 2 * kLutSize; i += kBlock) ws.lut[i] = lut[i];
+  if (tid == 0) {
+    const int flag = bad == INT_MAX ? 0 : bad + 1;
+    ws.head[0] = count[0];
+    ws.head[1] = count[1];
+    ws.head[2] = flag;
+    ws.head[3] = 0;
+    status[0] = 0;
+    status[1] = ULLONG_MAX;   // minimum of 1 + row; unpack_end_kernel
+    status[2] = (u64)flag;
+  }
+}
+
+__global__ void unpack_end_kernel(u64* status) {
+  if (status[1] == ULLONG_MAX) status[1] = 0;
+}
+
+// ---- the bit reader of one lane ---------------------------------------------
+// `win` holds the next `have` stream bits from `pos` on, left-aligned, zeros
+// behind them.  A byte is loaded only when its index is below `nbytes` and
+// its first bit below `end`; what a caller may use of the window is avail():
+// the bits that are loaded AND belong to the row.
+struct BitReader {
+  const uint8_t* bytes;
+  int64_t nbytes;   // packed_bytes
+  int64_t end;      // the row's end, at most 8 * nbytes
+  int64_t pos;      // >= 0
+  int64_t next;     // index of the next byte to load
+  u64 win;
+  int have;
+
+  __device__ __forceinline__ bool loadable() const {
+    return next < nbytes && next * 8 < end;
+  }
+  __device__ __forceinline__ void seek(int64_t to) {
+    pos = to;
+    next = to >> 3;
+    win = 0;
+    have = 0;
+    const int skip = (int)(to & 7);
+    if (skip && loadable()) {   // the bits before `to` fall off the top
+      win = (u64)bytes[next] << (56 + skip);
+      have = 8 - skip;
+      ++next;
+    }
+  }
+  __device__ __forceinline__ void refill() {
+    while (have <= 56 && loadable()) {
+      win |= (u64)bytes[next] << (56 - have);
+      have += 8;
+      ++next;
+    }
+  }
+  // After refill(): the 64 bits from pos on.  refill() stops at 57..64 bits;
+  // the top of one more byte completes them, without being consumed.
+  __device__ __forceinline__ u64 window64() const {
+    if (have >= 57 && have < 64 && loadable())
+      return win | (u64)bytes[next] >> (have - 56);
+    return win;
+  }
+  __device__ __forceinline__ int64_t avail() const {
+    const int64_t left = end - pos;
+    return left < have ? left : have;
+  }
+  // the same for window64()
+  __device__ __forceinline__ int64_t avail64() const {
+    const int64_t left = end - pos;
+    const int loaded = have >= 57 && have < 64 && loadable() ? 64 : have;
+    return left < loaded ? left : loaded;
+  }
+  __device__ __forceinline__ void consume(int n) {
+    if (n < have) {
+      win <<= n;
+      have -= n;
+      pos += n;
+    } else {
+      seek(pos + n);
+    }
+  }
+};
+
+// The codeword the window starts with, as a meta word; 0 when none does.
+// lut, code, meta: one table's arrays in LDS; n: its codewords.
+__device__ __forceinline__ unsigned match(const uint16_t* lut, const u64* code,
+                                          const uint16_t* meta, int n, u64 w) {
+  const unsigned e = lut[w >> (kMaxCodeBits - kLutBits)];
+  if (e) return e;
+  int lo = 0, hi = n;   // lo: number of codewords <= w
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (code[mid] <= w)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  if (lo == 0) return 0;
+  const unsigned m = meta[lo - 1];
+  if ((code[lo - 1] ^ w) >> (kMaxCodeBits - (m >> 9))) return 0;
+  return m;
+}
+
+// Reads one codeword of a table: its symbol id, or -1 (no match, or the match
+// passes the row's end or the buffer).
+__device__ __forceinline__ int read_symbol(BitReader& r, const uint16_t* lut,
+                                           const u64* code,
+                                           const uint16_t* meta, int n) {
+  r.refill();
+  const unsigned m = match(lut, code, meta, n, r.window64());
+  const int l = m >> 9;
+  if (!m || l > r.avail64()) return -1;
+  r.consume(l);
+  return m & 511;
+}
+
+// Reads `size` value bits, 1..15; false when they pass the end.
+__device__ __forceinline__ bool read_value(BitReader& r, int size,
+                                           int32_t* value) {
+  r.refill();
+  if (size > r.avail()) return false;
+  const int32_t bits = (int32_t)(r.win >> (kMaxCodeBits - size));
+  r.consume(size);
+  *value = (bits >> (size - 1)) ? bits : bits - ((1 << size) - 1);
+  return true;
+}
+
+// One row.  false: malformed; what was decoded before the fault is stored.
+__device__ __forceinline__ bool unpack_row(
+    BitReader& r, int64_t begin, int64_t stop, int32_t* __restrict__ row,
+    int s, const uint16_t* lut, const u64* code, const uint16_t* meta,
+    int n_ac, int n_dc) {
+  if (begin < 0 || begin > stop) return false;
+  r.seek(begin);
+  int k = 1;
+  for (;;) {   // every turn consumes at least one bit of a finite row
+    const int b = read_symbol(r, lut, code, meta, n_ac);
+    if (b < 0) return false;
+    if (b == kEob) break;
+    if (b == kZrl) {
+      if (k < s) k += 16;   // beyond s only "beyond s" matters: no overflow
+      continue;
+    }
+    const int size = b & 15;
+    if (size == 0) return false;
+    if (k < s) k += b >> 4;
+    if (k >= s) return false;
+    int32_t v;
+    if (!read_value(r, size, &v)) return false;
+    row[k] = v;   // 1 <= k < s
+    ++k;
+  }
+  const int c = read_symbol(r, lut + kLutSize, code + kDcBase, meta + kDcBase,
+                            n_dc);
+  if (c < 0) return false;
+  if (c > kDcBase) {
+    int32_t v;
+    if (!read_value(r, c - kDcBase, &v)) return false;
+    row[0] = v;
+  }
+  return r.pos == stop;
+}
+
+__global__ __launch_bounds__(kBlock) void unpack_kernel(
+    const uint8_t* __restrict__ packed, int64_t packed_bytes,
+    const long long* __restrict__ offsets, int64_t d, int s, DecodeLayout ws,
+    int32_t* __restrict__ levels, u64* __restrict__ status) {
+  __shared__ u64 code[kSymbols];
+  __shared__ uint16_t meta[kSymbols];
+  __shared__ uint16_t lut[2 * kLutSize];
+  if (ws.head[2]) return;   // not prefix-free: nothing is decoded
+  const int n_ac = ws.head[0], n_dc = ws.head[1];
+  for (int i = threadIdx.x; i < kSymbols; i += kBlock) {
+    code[i] = ws.code[i];
+    meta[i] = ws.meta[i];
+  }
+  for (int i = threadIdx.x; i < 2 * kLutSize; i += kBlock) lut[i] = ws.lut[i];
+  __syncthreads();
+
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  bool malformed = false;
+  if (p < d) {
+    const int64_t begin = offsets[p], stop = offsets[p + 1];
+    const int64_t limit = packed_bytes * 8;
+    BitReader r;
+    r.bytes = packed;
+    r.nbytes = packed_bytes;
+    r.end = stop < limit ? stop : limit;
+    malformed = !unpack_row(r, begin, stop, levels + p * s, s, lut, code, meta,
+                            n_ac, n_dc);
+  }
+  // rows of a wave are consecutive: its first malformed row is its lowest lane
+  const u64 mask = __ballot(malformed);
+  if (mask && (threadIdx.x & 63) == 0) {
+    atomicAdd(&status[0], (u64)__popcll(mask));
+    atomicMin(&status[1], (u64)(p + __ffsll((long long)mask)));
+  }
+}
+
+int check_rows(const char* who, int64_t d, int32_t s, int64_t* blocks) {
+  VTC_REQUIRE(d > 0, "%s: bad size d = %lld", who, (long long)d);
+  VTC_REQUIRE(s >= 1 && s <= VTC_JPEG_MAX_S,
+              "%s: bad size s = %d (1 .. %d)", who, s, VTC_JPEG_MAX_S);
+  *blocks = ceil_div(d, kBlock);
+  VTC_REQUIRE(*blocks < (int64_t)1 << 31, "%s: too many rows", who);
+  return VTC_OK;
+}
+
+}  // namespace
+}  // namespace vtc
+
+using namespace vtc;
+
+extern "C" int vtc_decode_abi_version(void) { return VTC_DECODE_ABI_VERSION; }
+
+extern "C" size_t vtc_jpeg_unpack_workspace_bytes(void) {
+  return measured_bytes<DecodeLayout>();
+}
+
+extern "C" int vtc_jpeg_unpack(const uint8_t* packed, size_t packed_bytes,
+                               const int64_t* offsets, int64_t d, int32_t s,
+                               const uint64_t* ac_code, const uint8_t* ac_len,
+                               const uint64_t* dc_code, const uint8_t* dc_len,
+                               int32_t* levels, int64_t* status,
+                               void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  const char* who = "vtc_jpeg_unpack";
+  VTC_REQUIRE(packed && offsets && ac_code && ac_len && dc_code && dc_len &&
+                  levels && status, "%s: null pointer", who);
+  int64_t blocks;
+  const int rc = check_rows(who, d, s, &blocks);
+  if (rc != VTC_OK) return rc;
+  VTC_REQUIRE(packed_bytes > 0 && packed_bytes < (size_t)1 << 59,
+              "%s: bad size packed_bytes = %zu", who, packed_bytes);
+  const size_t need = vtc_jpeg_unpack_workspace_bytes();
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+              need);
+    return VTC_ERR_WORKSPACE;
+  }
+  Carver carve(workspace);
+  const DecodeLayout ws(carve);
+  hipStream_t st = as_stream(stream);
+  u64* flags = reinterpret_cast<u64*>(status);
+  VTC_HIP_CHECK(hipMemsetAsync(levels, 0,
+                               (size_t)d * (size_t)s * sizeof(int32_t), st));
+  decode_tables_kernel<<<1, kBlock, 0, st>>>(
+      reinterpret_cast<const u64*>(ac_code), ac_len,
+      reinterpret_cast<const u64*>(dc_code), dc_len, ws, flags);
+  unpack_kernel<<<(int)blocks, kBlock, 0, st>>>(
+      packed, (int64_t)packed_bytes, reinterpret_cast<const long long*>(offsets),
+      d, s, ws, levels, flags);
+  unpack_end_kernel<<<1, 1, 0, st>>>(flags);
+  VTC_LAUNCH_CHECK();
+  return VTC_OK;
+}

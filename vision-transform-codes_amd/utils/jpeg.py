@@ -12,6 +12,11 @@ runs in the kernels of csrc/jpeg_codec.hip behind include/vtc_codec.h; the
 Huffman tables, at most 272 symbols, are built here on the host from the
 device counts.  DESIGN.md 4.11 states the coding rules.
 
+The reference has no decoder: it only measures len(stream).  Here the packed
+streams can be read back -- unpack_streams, parse_jpg_binary_stream (the
+inverse of generate_jpg_binary_stream for one row), decode_patches -- through
+csrc/jpeg_decode.hip behind include/vtc_decode.h; DESIGN.md 4.12.
+
 Symbols are spelled as the reference spells them: an AC byte b is
 '%x%x' % (b >> 4, b & 15), DC category 0 is '-', category c is '%x' % c.
 Tables are dicts {symbol: string of '0' / '1'}.
@@ -305,6 +310,85 @@ def stream_as_str(packed, offsets, i):
   return ''.join('1' if b else '0' for b in bits)
 
 
+# ------------------------------------------------------------------ decoding
+def check_prefix_free(table):
+  """ValueError naming two symbols of a {symbol: codeword} table when the
+  codeword of one equals the other's or is a prefix of it: such a table
+  cannot be decoded.  In sorted order a prefix sits right before a word that
+  starts with it, so neighbours suffice."""
+  words = sorted((word, symbol) for symbol, word in table.items())
+  for (short, first), (long_, second) in zip(words, words[1:]):
+    if long_.startswith(short):
+      raise ValueError(
+          'not a prefix-free table: the codeword %r of symbol %r %s the '
+          'codeword %r of symbol %r' % (
+              short, first, 'equals' if short == long_ else 'is a prefix of',
+              long_, second))
+
+
+def unpack_streams(packed, offsets, s, table_ac, table_dc):
+  """levels (d, s) int32 device tensor from what pack_streams returns: packed
+  is a uint8 device tensor, offsets the (d + 1,) int64 device tensor of the bit
+  at which each row's stream starts, the total last.  The inverse of
+  pack_streams under the same two tables.
+
+  ValueError for a table that is not prefix-free (both symbols named) and for
+  malformed rows (their number and the first one named; include/vtc_decode.h
+  lists what makes a row malformed), NotImplementedError for a codeword of
+  more than 64 bits, VtcHipError for a CPU tensor.  One host read (the
+  status)."""
+  for table in (table_ac, table_dc):
+    check_prefix_free(table)
+  packed =vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
+  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
+  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] < 2:
+    raise ValueError('packed must be (bytes,) and offsets (d + 1,), got '
+                     'shapes %s and %s' % (tuple(packed.shape),
+                                           tuple(offsets.shape)))
+  lib = vtc_hip.load_library()
+  packed, offsets = packed.contiguous(), offsets.contiguous()
+  device = packed.device
+  d, s = offsets.shape[0] - 1, int(s)
+  tables = _DeviceTables(table_ac, table_dc, device)
+  levels = torch.empty((d, s), dtype=torch.int32, device=device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  ws = vtc_hip.workspace(lib.vtc_jpeg_unpack_workspace_bytes(), device)
+  vtc_hip.check(lib.vtc_jpeg_unpack(
+      vtc_hip.ptr(packed), packed.numel(), vtc_hip.ptr(offsets), d, s,
+      vtc_hip.ptr(tables.ac_code), vtc_hip.ptr(tables.ac_len),
+      vtc_hip.ptr(tables.dc_code), vtc_hip.ptr(tables.dc_len),
+      vtc_hip.ptr(levels), vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), 'vtc_jpeg_unpack')
+  malformed, first, clash = status.tolist()
+  if clash:   # the host check above saw the same tables
+    raise ValueError('not a prefix-free table: symbol %r'
+                     % _symbol_of_id(clash - 1))
+  if malformed:
+    raise ValueError('unpack_streams: %d malformed rows of %d, the first is '
+                     'row %d' % (malformed, d, first - 1))
+  return levels
+
+
+def decode_patches(packed, offsets, dictionary, binwidths, quant_multiplier,
+                   tables, order=None):
+  """The reconstruction (d, n) float32 of the patches whose streams are in
+  (packed, offsets): unpack_streams, dequantize with binwidths *
+  quant_multiplier, then invertible_linear.apply_filter with the dictionary.
+  With the arguments of rate_distortion_point it gives the reconstruction that
+  function takes its pSNR from, but from the bytes.
+
+  dictionary : (n, n) float32 device tensor
+  tables : (huff_table_ac, huff_table_dc)
+  """
+  from analysis_transforms.fully_connected import invertible_linear
+  dictionary = vtc_hip.require_device_tensor(dictionary, 'dictionary')
+  widths = np.asarray(binwidths, dtype=np.float64) * quant_multiplier
+  levels = unpack_streams(packed, offsets, dictionary.shape[0], tables[0],
+                          tables[1])
+  return invertible_linear.apply_filter(dequantize(levels, widths, order),
+                                        dictionary.contiguous())
+
+
 # ------------------------------------------------- the reference's interface
 def _relative_levels(assignment_inds, inds_of_zero_valued_cw):
   """int32 levels relative to the zero codeword.  The subtraction and the
@@ -364,6 +448,30 @@ def generate_jpg_binary_stream(assignment_inds, inds_of_zero_valued_cw,
   assert (huffman_table_dc is not None) and (huffman_table_ac is not None)
   packed, offsets = pack_streams(levels, huffman_table_ac, huffman_table_dc)
   return stream_as_str(packed, offsets, 0)
+
+
+def parse_jpg_binary_stream(stream, s, inds_of_zero_valued_cw,
+                            huffman_table_ac, huffman_table_dc):
+  """The inverse of generate_jpg_binary_stream(...,
+  only_get_huffman_symbols=False) for one data point: the (s,) int64 device
+  tensor of assignment indices whose stream is the string `stream` of '0' and
+  '1'.  Through the batch path with d = 1, on the current HIP device (that of
+  inds_of_zero_valued_cw when it is a device tensor)."""
+  if not isinstance(stream, str) or set(stream) - set('01'):
+    raise TypeError("stream must be a str of '0' and '1'")
+  device = torch.device('cuda')
+  if torch.is_tensor(inds_of_zero_valued_cw) and inds_of_zero_valued_cw.is_cuda:
+    device = inds_of_zero_valued_cw.device
+    zero = inds_of_zero_valued_cw.to(torch.int64)
+  else:
+    zero = torch.as_tensor(np.asarray(inds_of_zero_valued_cw),
+                           dtype=torch.int64)
+  bits = np.frombuffer(stream.encode('ascii'), dtype=np.uint8) - ord('0')
+  host = np.packbits(bits) if len(stream) else np.zeros(1, dtype=np.uint8)
+  ends = np.array([0, len(stream)], dtype=np.int64)
+  levels = unpack_streams(_upload(host, device), _upload(ends, device), s,
+                          huffman_table_ac, huffman_table_dc)
+  return levels[0].to(torch.int64) + zero.to(device)
 
 
 def rate_distortion_point(patches, dictionary, binwidths, quant_multiplier,

@@ -1,6 +1,6 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
-include/vtc_image.h and include/vtc_codec.h).
+include/vtc_image.h, include/vtc_codec.h and include/vtc_decode.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -191,6 +191,17 @@ CODEC_SIGNATURES = {
                              _sz, _vp, _vp]),
 }
 
+DECODE_ABI_VERSION = 1   # VTC_DECODE_ABI_VERSION of include/vtc_decode.h
+
+# The fourth header, include/vtc_decode.h (same library): packed JPEG streams
+# back to levels.  Again a table of its own.
+DECODE_SIGNATURES = {
+    'vtc_decode_abi_version': (_i32, []),
+    'vtc_jpeg_unpack_workspace_bytes': (_sz, []),
+    'vtc_jpeg_unpack': (_i32, [_vp, _sz, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _sz, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -207,7 +218,8 @@ def load_library():
         '(hipcc --offload-arch=gfx950).  There is no CPU fallback.'
         % (LIBRARY_PATH, _PKG_ROOT / 'csrc'))
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
-  for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES):
+  for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
+                DECODE_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -218,6 +230,8 @@ def load_library():
     raise ImportError('libvtc_hip.so image ABI version mismatch')
   if lib.vtc_codec_abi_version() != CODEC_ABI_VERSION:
     raise ImportError('libvtc_hip.so codec ABI version mismatch')
+  if lib.vtc_decode_abi_version() != DECODE_ABI_VERSION:
+    raise ImportError('libvtc_hip.so decode ABI version mismatch')
   _lib = lib
   return lib
 
