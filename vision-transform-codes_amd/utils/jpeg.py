@@ -6,8 +6,9 @@ The reference's names are kept, with their return types --
 get_jpeg_quant_hifi_binwidths, compute_huffman_table, jpg_coeff_to_binstr,
 generate_ac_dc_huffman_tables, generate_jpg_binary_stream -- and beside them
 a batch interface the reference lacks: quantize, dequantize, symbol_counts,
-stream_bits, pack_streams, stream_as_str, rate_distortion_point.  The
-per-patch work (run-length symbols, their counts, stream lengths, packing)
+stream_bits, pack_streams, stream_as_str, rate_distortion_point,
+rate_distortion_image (a whole image tiled, coded, decoded and reassembled,
+with pSNR and SSIM measured on the image).  The per-patch work (run-length symbols, their counts, stream lengths, packing)
 runs in the kernels of csrc/jpeg_codec.hip behind include/vtc_codec.h; the
 Huffman tables, at most 272 symbols, are built here on the host from the
 device counts.  DESIGN.md 4.11 states the coding rules.
@@ -503,3 +504,77 @@ def rate_distortion_point(patches, dictionary, binwidths, quant_multiplier,
       dequantize(levels, widths, order), dictionary.contiguous())
   psnr = plotting.compute_pSNR(patches, reconstruction)
   return total_bits / float(patches.numel()), psnr, tables
+
+
+def _component_means(component_means, n, device):
+  if torch.is_tensor(component_means):
+    means = component_means.to(device=device, dtype=torch.float32)
+  else:
+    means = _upload(np.asarray(component_means, dtype=np.float32), device)
+  means = means.reshape(-1).contiguous()
+  if means.shape[0] != n:
+    raise ValueError('component_means must have %d entries, got %d'
+                     % (n, means.shape[0]))
+  return means
+
+
+def rate_distortion_image(image, dictionary, patch_dimensions, binwidths,
+                          quant_multiplier, tables=None, order=None,
+                          component_means=None):
+  """One point of a rate-distortion curve, measured on a whole image as the
+  reference's experiments do (their fullimg_reshape_params): the image is
+  tiled into patches, the patches are coded, quantised, packed into their
+  JPEG streams, decoded from those bytes (decode_patches) and reassembled,
+  and both distortions are taken between the reassembled image and the part
+  of the original that the patches cover.
+
+  image : (h, w) float32 device tensor
+  dictionary : (n, n) float32 device tensor, n = ph * pw, patches ~ codes @
+      dictionary
+  patch_dimensions : (ph, pw); pixels right of and below the last whole patch
+      are left out of every figure
+  binwidths, quant_multiplier, tables, order : as in rate_distortion_point
+  component_means : None, or n values subtracted from every patch before it
+      is coded and added back after decoding, as the reference's experiments
+      centre their patches
+
+  Returns {'bits_per_pixel', 'pSNR', 'SSIM', 'tables'}: total stream bits over
+  covered pixels, plotting.compute_pSNR and plotting.compute_ssim of (covered
+  original, reassembled reconstruction), and (huff_table_ac, huff_table_dc).
+  """
+  from analysis_transforms.fully_connected import invertible_linear
+  from utils import image_processing
+  from utils import plotting
+  image = vtc_hip.require_device_tensor(image, 'image')
+  if image.dim() != 2:
+    raise ValueError('image must be (h, w), got shape %s'
+                     % (tuple(image.shape),))
+  ph, pw = int(patch_dimensions[0]), int(patch_dimensions[1])
+  patches, positions = image_processing.patches_from_single_image(
+      image[:, :, None], (ph, pw), flatten_patches=True)
+  if patches.shape[0] == 0:
+    raise ValueError('image %s holds no %d x %d patch'
+                     % (tuple(image.shape), ph, pw))
+  original = image[:image.shape[0] // ph * ph, :image.shape[1] // pw * pw]
+  coded = patches
+  if component_means is not None:
+    means = _component_means(component_means, patches.shape[1], image.device)
+    coded = image_processing._column_apply(
+        patches, vtc_hip.DTYPE_F32, vtc_hip.COLUMN_SUBTRACT, means)
+  widths = np.asarray(binwidths, dtype=np.float64) * quant_multiplier
+  levels = quantize(invertible_linear.run(coded, dictionary), widths, order)
+  if tables is None:
+    tables = tables_from_counts(*symbol_counts(levels))
+  packed, offsets = pack_streams(levels, tables[0], tables[1])
+  total_bits = int(offsets[-1])
+  decoded = decode_patches(packed, offsets, dictionary, binwidths,
+                           quant_multiplier, tables, order)
+  if component_means is not None:   # x - (-m): the addition, in float32
+    decoded = image_processing._column_apply(
+        decoded, vtc_hip.DTYPE_F32, vtc_hip.COLUMN_SUBTRACT, -means)
+  reconstruction = image_processing.assemble_image_from_patches(
+      decoded, (ph, pw), positions)[:, :, 0]
+  return {'bits_per_pixel': total_bits / float(patches.numel()),
+          'pSNR': plotting.compute_pSNR(original, reconstruction),
+          'SSIM': plotting.compute_ssim(original, reconstruction),
+          'tables': tables}

@@ -1,6 +1,7 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
-include/vtc_image.h, include/vtc_codec.h and include/vtc_decode.h).
+include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h and
+include/vtc_quality.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -27,6 +28,7 @@ F32, BF16X3, BF16, F16X3 = range(4)
 PRECISIONS = {'f32': F32, 'bf16x3': BF16X3, 'bf16': BF16, 'f16x3': F16X3}
 LOCAL_LUMINANCE, LOCAL_CONTRAST = range(2)
 DTYPE_F32, DTYPE_U8 = range(2)
+DTYPE_F64 = 2   # VTC_DTYPE_F64 of include/vtc_quality.h
 COLUMN_SUBTRACT, COLUMN_DIVIDE_SQRT = range(2)
 ABI_VERSION = 4   # VTC_ABI_VERSION of include/vtc_hip.h this binding matches
 
@@ -202,6 +204,17 @@ DECODE_SIGNATURES = {
                                _vp, _vp, _vp, _sz, _vp]),
 }
 
+QUALITY_ABI_VERSION = 1   # VTC_QUALITY_ABI_VERSION of include/vtc_quality.h
+
+# The fifth header, include/vtc_quality.h (same library): SSIM of image
+# stacks.  Again a table of its own.
+QUALITY_SIGNATURES = {
+    'vtc_quality_abi_version': (_i32, []),
+    'vtc_ssim_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'vtc_ssim': (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp,
+                        _sz, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -219,7 +232,7 @@ def load_library():
         % (LIBRARY_PATH, _PKG_ROOT / 'csrc'))
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
-                DECODE_SIGNATURES):
+                DECODE_SIGNATURES, QUALITY_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -232,6 +245,8 @@ def load_library():
     raise ImportError('libvtc_hip.so codec ABI version mismatch')
   if lib.vtc_decode_abi_version() != DECODE_ABI_VERSION:
     raise ImportError('libvtc_hip.so decode ABI version mismatch')
+  if lib.vtc_quality_abi_version() != QUALITY_ABI_VERSION:
+    raise ImportError('libvtc_hip.so quality ABI version mismatch')
   _lib = lib
   return lib
 
