@@ -1,7 +1,7 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
-include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h and
-include/vtc_quality.h).
+include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
+include/vtc_quality.h and include/vtc_stats.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -215,6 +215,29 @@ QUALITY_SIGNATURES = {
                         _sz, _vp]),
 }
 
+STATS_ABI_VERSION = 1   # VTC_STATS_ABI_VERSION of include/vtc_stats.h
+STATS_MAX_IGNORE, STATS_MAX_BINS, STATS_MAX_JOINT_BINS = 8, 4096, 256
+
+# The sixth header, include/vtc_stats.h (same library): column summaries,
+# marginal and joint histograms of codes, the mean per bin of a map.  Again a
+# table of its own.
+STATS_SIGNATURES = {
+    'vtc_stats_abi_version': (_i32, []),
+    'vtc_code_summary_workspace_bytes': (_sz, [_i64, _i64]),
+    'vtc_code_summary': (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vtc_code_histogram_workspace_bytes': (_sz, [_i64, _i64, _i32]),
+    'vtc_code_histogram': (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _i32,
+                                  _vp, _vp, _sz, _vp]),
+    'vtc_code_joint_histogram_workspace_bytes': (_sz, [_i64, _i64]),
+    'vtc_code_joint_histogram': (_i32, [_vp, _i64, _i64, _vp, _i64, _i32,
+                                        _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                        _vp, _sz, _vp]),
+    'vtc_binned_mean_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
+    'vtc_binned_mean': (_i32, [_vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
+                               _vp, _vp, _sz, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -232,7 +255,7 @@ def load_library():
         % (LIBRARY_PATH, _PKG_ROOT / 'csrc'))
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
-                DECODE_SIGNATURES, QUALITY_SIGNATURES):
+                DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -247,6 +270,8 @@ def load_library():
     raise ImportError('libvtc_hip.so decode ABI version mismatch')
   if lib.vtc_quality_abi_version() != QUALITY_ABI_VERSION:
     raise ImportError('libvtc_hip.so quality ABI version mismatch')
+  if lib.vtc_stats_abi_version() != STATS_ABI_VERSION:
+    raise ImportError('libvtc_hip.so stats ABI version mismatch')
   _lib = lib
   return lib
 
