@@ -1,7 +1,7 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
-include/vtc_quality.h and include/vtc_stats.h).
+include/vtc_quality.h, include/vtc_stats.h and include/vtc_quant.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -238,6 +238,34 @@ STATS_SIGNATURES = {
                                _vp, _vp, _sz, _vp]),
 }
 
+QUANT_ABI_VERSION = 1   # VTC_QUANT_ABI_VERSION of include/vtc_quant.h
+QUANT_MAX_CODEWORDS, QUANT_ROWS = 1024, 512
+
+
+class QuantState(ctypes.Structure):
+  """struct vtc_quant_state of include/vtc_quant.h."""
+  _fields_ = [('codebooks', ctypes.c_void_p), ('lengths', ctypes.c_void_p),
+              ('counts', ctypes.c_void_p), ('cost', ctypes.c_void_p),
+              ('k', ctypes.c_void_p), ('zero_index', ctypes.c_void_p),
+              ('active', ctypes.c_void_p), ('iterations', ctypes.c_void_p)]
+
+
+_QSTATE_P = ctypes.POINTER(QuantState)
+_f64 = ctypes.c_double
+
+# The seventh header, include/vtc_quant.h (same library): per-column scalar
+# quantisers, one Lloyd step, index counts.  Again a table of its own.
+QUANT_SIGNATURES = {
+    'vtc_quant_abi_version': (_i32, []),
+    'vtc_quant_assign': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _f64,
+                                _vp, _vp, _vp, _vp]),
+    'vtc_quant_lloyd_step_workspace_bytes': (_sz, [_i64, _i64, _i32]),
+    'vtc_quant_lloyd_step': (_i32, [_vp, _i64, _i64, _i32, _f64, _f64, _i32,
+                                    _QSTATE_P, _QSTATE_P, _vp, _vp, _sz,
+                                    _vp]),
+    'vtc_quant_index_counts': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -255,7 +283,8 @@ def load_library():
         % (LIBRARY_PATH, _PKG_ROOT / 'csrc'))
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
-                DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES):
+                DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
+                QUANT_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -272,6 +301,8 @@ def load_library():
     raise ImportError('libvtc_hip.so quality ABI version mismatch')
   if lib.vtc_stats_abi_version() != STATS_ABI_VERSION:
     raise ImportError('libvtc_hip.so stats ABI version mismatch')
+  if lib.vtc_quant_abi_version() != QUANT_ABI_VERSION:
+    raise ImportError('libvtc_hip.so quant ABI version mismatch')
   _lib = lib
   return lib
 
