@@ -32,8 +32,9 @@ host read gathers active, iterations, cost and the status word through one
 float64 torch.cat (int32 and the counts of NaN codes up to 2^53 are exact in
 float64), so that a fit costs one device-to-host copy.
 
-The vector quantiser of the experiment's Mod2 / Mod3 variants is not part of
-this module.
+The vector quantiser of the experiment's Mod2 / Mod3 variants lives in
+utils.vector_quantization (include/vtc_vq.h), a superset of
+this module: `from utils import vector_quantization as quantization`.
 """
 import ctypes
 
@@ -332,6 +333,28 @@ def entropy_bits(counts):
   return float(terms.sum(1).sum())
 
 
+def _distortion(patches, reconstruction, fullimg_reshape_params):
+  """The distortion dictionary of compute_RD_point (its docstring)."""
+  from utils import plotting
+  distortion = {'pSNR': plotting.compute_pSNR(patches, reconstruction)}
+  if fullimg_reshape_params is not None:
+    from utils import image_processing
+    dims = fullimg_reshape_params['patch_dim']
+    positions = fullimg_reshape_params['patch_positions']
+    original = image_processing.assemble_image_from_patches(
+        patches, dims, positions)
+    image = image_processing.assemble_image_from_patches(
+        reconstruction, dims, positions)
+    if original.shape[2] != 1:
+      raise ValueError('full-image distortion is defined for one channel')
+    distortion = {'pSNR_patches': distortion['pSNR'],
+                  'pSNR': plotting.compute_pSNR(original[:, :, 0].contiguous(),
+                                                image[:, :, 0].contiguous()),
+                  'SSIM': plotting.compute_ssim(original[:, :, 0].contiguous(),
+                                                image[:, :, 0].contiguous())}
+  return distortion
+
+
 def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
                      lagrange_mult=0.0, source_code='jpeg', tables=None,
                      fullimg_reshape_params=None):
@@ -356,7 +379,6 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   'SSIM'} of the images, with the patch figure under 'pSNR_patches'.
   """
   from utils import jpeg
-  from utils import plotting
   if source_code not in ('jpeg', 'entropy'):
     raise ValueError("source_code must be 'jpeg' or 'entropy'")
   codes = _codes(codes)
@@ -389,23 +411,8 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   if int(status) != 0:
     raise ValueError('compute_RD_point: the codes hold NaN')
   rate = total_bits / float(patches.numel())
-  distortion = {'pSNR': plotting.compute_pSNR(patches, reconstruction)}
-  if fullimg_reshape_params is not None:
-    from utils import image_processing
-    dims = fullimg_reshape_params['patch_dim']
-    positions = fullimg_reshape_params['patch_positions']
-    original = image_processing.assemble_image_from_patches(
-        patches, dims, positions)
-    image = image_processing.assemble_image_from_patches(
-        reconstruction, dims, positions)
-    if original.shape[2] != 1:
-      raise ValueError('full-image distortion is defined for one channel')
-    distortion = {'pSNR_patches': distortion['pSNR'],
-                  'pSNR': plotting.compute_pSNR(original[:, :, 0].contiguous(),
-                                                image[:, :, 0].contiguous()),
-                  'SSIM': plotting.compute_ssim(original[:, :, 0].contiguous(),
-                                                image[:, :, 0].contiguous())}
-  return rate, distortion, tables
+  return rate, _distortion(patches, reconstruction,
+                           fullimg_reshape_params), tables
 
 
 def _uniform_for(codes, binwidths, quant_multiplier):

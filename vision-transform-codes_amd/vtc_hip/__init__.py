@@ -1,7 +1,8 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
-include/vtc_quality.h, include/vtc_stats.h and include/vtc_quant.h).
+include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h and
+include/vtc_vq.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -266,6 +267,34 @@ QUANT_SIGNATURES = {
     'vtc_quant_index_counts': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp]),
 }
 
+VQ_ABI_VERSION = 1   # VTC_VQ_ABI_VERSION of include/vtc_vq.h
+VQ_MAX_DIM, VQ_MAX_CODEWORDS = 32, 4096
+VQ_TILE_DOUBLES, VQ_ROWS = 4096, 2048
+
+
+class VqState(ctypes.Structure):
+  """struct vtc_vq_state of include/vtc_vq.h."""
+  _fields_ = [('codebook', ctypes.c_void_p), ('lengths', ctypes.c_void_p),
+              ('counts', ctypes.c_void_p), ('cost', ctypes.c_void_p),
+              ('k', ctypes.c_void_p), ('zero_index', ctypes.c_void_p),
+              ('active', ctypes.c_void_p), ('iterations', ctypes.c_void_p)]
+
+
+_VQSTATE_P = ctypes.POINTER(VqState)
+
+# The eighth header, include/vtc_vq.h (same library): one vector quantiser for
+# the rows of a (b, d) array, one Lloyd step, index counts.  Again a table of
+# its own.
+VQ_SIGNATURES = {
+    'vtc_vq_abi_version': (_i32, []),
+    'vtc_vq_assign': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _f64, _vp,
+                             _vp, _vp, _vp]),
+    'vtc_vq_lloyd_step_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'vtc_vq_lloyd_step': (_i32, [_vp, _i64, _i32, _i32, _f64, _f64, _i32,
+                                 _VQSTATE_P, _VQSTATE_P, _vp, _vp, _sz, _vp]),
+    'vtc_vq_index_counts': (_i32, [_vp, _i64, _i32, _vp, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -284,7 +313,7 @@ def load_library():
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
-                QUANT_SIGNATURES):
+                QUANT_SIGNATURES, VQ_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -303,6 +332,8 @@ def load_library():
     raise ImportError('libvtc_hip.so stats ABI version mismatch')
   if lib.vtc_quant_abi_version() != QUANT_ABI_VERSION:
     raise ImportError('libvtc_hip.so quant ABI version mismatch')
+  if lib.vtc_vq_abi_version() != VQ_ABI_VERSION:
+    raise ImportError('libvtc_hip.so vector quantiser ABI version mismatch')
   _lib = lib
   return lib
 
