@@ -1,6 +1,7 @@
 // Device helpers shared by the fused persistent kernels (fc_fused.hip: state on
 // chip; fused_stream.hip: state streamed): dictionary packing into MFMA
-// fragment order, the f16 dictionary scale, buffer loads, stamps.  The hi/lo
+// fragment order (32x32x16 operands, or 16x16x32 ones for fc_fused.hip's
+// second tile), the f16 dictionary scale, buffer loads, stamps.  The hi/lo
 // operand split and the MFMA wrapper are split_operand.h's.
 #pragma once
 #include "common.h"
@@ -18,6 +19,14 @@ constexpr int kPhaseAtoms = 128;
 // packT fragment (phase p, pixel block nb of 32, k-step ks over the phase's
 // atoms), lane l:
 //   D[128p + 16ks + 8(l>>5) + j][32nb + (l&31)]
+// TILE16, the same tiles as 16x16x32 operands (fc_fused.hip): still 16 one-KiB
+// fragments per wave and segment, the same bytes in the same workspace.
+// packA fragment (tile t, 16-atom half m, k-step ks over 32 pixels; fragment
+// t*16 + 2ks + m), lane l:
+//   D[32t + 16m + (l&15)][32ks + 8(l>>4) + j]
+// packT fragment (phase p, pixel block nb of 16, k-step ks over 32 of the
+// phase's atoms; fragment (16p + nb)*4 + ks), lane l:
+//   D[128p + 32ks + 8(l>>4) + j][16nb + (l&15)]
 
 // F16: sigma_D = 2^(8 - floor(log2 max|D|)), so that max |sigma_D D| lies in
 // [256, 512): far from the f16 overflow (65504) and with the lo parts of all
@@ -54,7 +63,7 @@ static __global__ __launch_bounds__(1024) void dictionary_scale_kernel(
 }
 
 // Both parts in one pass (loA / loT null: hi part only).
-template <bool F16>
+template <bool F16, bool TILE16 = false>
 __global__ void pack_dictionary_kernel(const float* __restrict__ D, int s,
                                        unsigned short* __restrict__ packA,
                                        unsigned short* __restrict__ packT,
@@ -66,11 +75,14 @@ __global__ void pack_dictionary_kernel(const float* __restrict__ D, int s,
   for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < frags;
        u += (int64_t)gridDim.x * blockDim.x) {
     const int l = (int)(u & 63);
-    const int r = l & 31, h = l >> 5;
+    const int r = TILE16 ? (l & 15) : (l & 31), h = TILE16 ? (l >> 4) : (l >> 5);
     {
-      const int64_t f = u >> 6;  // = t*16 + ks
+      const int64_t f = u >> 6;  // = t*16 + ks, TILE16: t*16 + 2ks + m
       const int t = (int)(f >> 4), ks = (int)(f & 15);
-      const float* src = D + (int64_t)(32 * t + r) * kFN + 16 * ks + 8 * h;
+      const float* src =
+          TILE16 ? D + (int64_t)(32 * t + 16 * (ks & 1) + r) * kFN +
+                       32 * (ks >> 1) + 8 * h
+                 : D + (int64_t)(32 * t + r) * kFN + 16 * ks + 8 * h;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = src[j] * sg;
@@ -79,10 +91,12 @@ __global__ void pack_dictionary_kernel(const float* __restrict__ D, int s,
       }
     }
     {
-      const int64_t f = u >> 6;  // = (p*8 + nb)*8 + ks
-      const int ks = (int)(f & 7), nb = (int)((f >> 3) & 7), p = (int)(f >> 6);
+      const int64_t f = u >> 6;  // = (p*8 + nb)*8 + ks, TILE16: (p*16 + nb)*4 + ks
+      const int ks = (int)(f & (TILE16 ? 3 : 7)), p = (int)(f >> 6);
+      const int nb = TILE16 ? (int)((f >> 2) & 15) : (int)((f >> 3) & 7);
       const float* src =
-          D + (int64_t)(128 * p + 16 * ks + 8 * h) * kFN + 32 * nb + r;
+          TILE16 ? D + (int64_t)(128 * p + 32 * ks + 8 * h) * kFN + 16 * nb + r
+                 : D + (int64_t)(128 * p + 16 * ks + 8 * h) * kFN + 32 * nb + r;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = src[(int64_t)j * kFN] * sg;

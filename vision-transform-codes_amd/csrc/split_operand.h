@@ -4,8 +4,10 @@
 // A float32 operand x becomes two 16-bit parts,
 //   hi = cvt(x),  lo = cvt(x - float(hi))      (round to nearest even)
 // and a product is formed on the matrix cores as hi*hi + hi*lo + lo*hi with
-// v_mfma_f32_32x32x16_{bf16,f16}, f32 accumulate: 3 MFMA per algorithmic
-// product, 5.3x the peak of the exact-f32 MFMA of gemm_f32.h.  Two part types
+// v_mfma_f32_32x32x16_{bf16,f16} (mfma16) or v_mfma_f32_16x16x32_{bf16,f16}
+// (mfma_k32: same rate per clock, a higher clock under load), f32 accumulate:
+// 3 MFMA per algorithmic product, 5.3x the peak of the exact-f32 MFMA of
+// gemm_f32.h.  Two part types
 // behind one template flag, same MFMA rate and same bytes:
 //   F16 = false ("bf16x3"): bf16 parts, 8 + 8 significand bits, ~2^-16
 //     relative per product: 1.6e-5 from the reference after 200 iterations,
@@ -30,6 +32,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // the part type of a split, and W parts as packed words / as a vector
 template <bool F16> struct split_part_type { typedef __bf16 type; };
@@ -55,6 +58,21 @@ __device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b,
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(
         __builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+      __builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// one 16x16x32 product of two fragments of 8 parts per lane: lane l holds
+// A[row l&15][k = 8(l>>4) + j] and B[k = 8(l>>4) + j][col l&15], and element e
+// of the result is C[row 4(l>>4) + e][col l&15].  Same cycles per FLOP as the
+// 32x32x16 form, but the chip holds a higher clock on it under load
+// (profiles/fused_mfma_shape.txt).
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma_k32(const uint4& a, const uint4& b,
+                                          const f32x4& c) {
+  if (F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(
+        __builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
       __builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
