@@ -1,0 +1,205 @@
+"""
+Huffman codes for the indices of the quantisers of utils.quantization and
+utils.vector_quantization: what a set of quantised sparse codes costs under
+tables trained elsewhere, and the bits themselves.
+
+The reference's experiment (experiments/rate_distortion_sparse_coding.py:
+763-827) trains one Huffman table per index stream on the training codes and
+charges the test codes what those tables cost.  Here
+
+  index_huffman_tables   counts of index_counts / vector_index_counts -> one
+                         table per column, on the host (at most 4096 symbols
+                         each), with jpeg.compute_huffman_table
+  index_table_arrays     tables -> the (m, kmax) arrays the device reads
+  index_code_bits        indices (b, m), tables -> bits per row and per column
+  pack_index_streams     indices (b, m), tables -> (packed, offsets), the
+                         layout of jpeg.pack_streams: jpeg.stream_as_str reads
+                         a row back as a string of '0' and '1'
+
+The per-entry work runs in the kernels of csrc/index_code.hip behind
+include/vtc_index_code.h.  Indices are (b, m) int32 device
+tensors: m index streams ("columns") per row, each with a table of its own,
+{int index: str of '0' / '1'}.  There is no decoder yet.
+"""
+import numpy as np
+import torch
+
+import vtc_hip
+from utils import jpeg
+
+ABSENT = vtc_hip.INDEX_CODE_ABSENT
+MAX_COLUMNS = vtc_hip.INDEX_CODE_MAX_COLUMNS
+MAX_SYMBOLS = vtc_hip.INDEX_CODE_MAX_SYMBOLS
+
+
+# ------------------------------------------------------------------ host side
+def _host_rows(counts):
+  """The rows of a 2-d count array as lists of Python integers (a weight may
+  exceed int64 in a constructed table)."""
+  if torch.is_tensor(counts):
+    counts = counts.cpu().numpy()
+  if isinstance(counts, np.ndarray):
+    if counts.ndim == 1:
+      counts = counts[None, :]
+    if counts.ndim != 2:
+      raise ValueError('counts must be (m, kmax), got shape %s'
+                       % (counts.shape,))
+    counts = counts.tolist()
+  rows = [[int(c) for c in row] for row in counts]
+  if not rows or not rows[0] or len(set(len(row) for row in rows)) != 1:
+    raise ValueError('counts must be (m, kmax) with m, kmax >= 1')
+  return rows
+
+
+def index_huffman_tables(counts, k=None):
+  """One Huffman table per column: a list of m dicts {index: codeword}.
+
+  counts : (m, kmax) integers, what quantization.index_counts or
+      vector_quantization.vector_index_counts (a [kmax] row is one column)
+      return for the training indices; device tensor, array or lists
+  k : the codewords in use of each column's codebook, m integers or one for
+      all; None for kmax
+
+  Every index i < k[j] that was not seen enters with weight 1, the rule
+  jpeg.tables_from_counts applies to unseen JPEG symbols; seen indices keep
+  their counts; indices >= k[j] are absent.  So every index that an `assign`
+  against the same codebook can produce is codable, whatever data it is run
+  on.  The code is jpeg.compute_huffman_table of those weights: its list
+  ordering settles ties deterministically for integer symbols.  A column with
+  k[j] = 1 gets {0: ''}, a code of no bits."""
+  rows = _host_rows(counts)
+  m, kmax = len(rows), len(rows[0])
+  if k is None:
+    k = [kmax] * m
+  else:
+    if torch.is_tensor(k):
+      k = k.cpu().numpy()
+    k = [int(v) for v in np.asarray(k).reshape(-1)]
+    if len(k) == 1:
+      k = k * m
+  if len(k) != m or min(k) < 1 or max(k) > kmax:
+    raise ValueError('k must hold %d values in [1, %d]' % (m, kmax))
+  return [jpeg.compute_huffman_table(
+      {i: (row[i] if row[i] > 0 else 1) for i in range(k[j])})
+          for j, row in enumerate(rows)]
+
+
+def tables_kmax(tables):
+  """The smallest kmax that holds every symbol of the tables."""
+  return max(max(table) for table in tables) + 1
+
+
+def index_table_arrays(tables, kmax):
+  """(code uint64 (m, kmax), len uint8 (m, kmax)) of a list of m tables: the
+  codeword right-aligned, 255 where the table lacks the symbol.  A codeword
+  of more than 64 bits raises NotImplementedError, as jpeg.table_arrays
+  does."""
+  m, kmax = len(tables), int(kmax)
+  code = np.zeros((m, kmax), dtype=np.uint64)
+  length = np.full((m, kmax), ABSENT, dtype=np.uint8)
+  for j, table in enumerate(tables):
+    for index, word in table.items():
+      if len(word) > jpeg.MAX_CODE_BITS:
+        raise NotImplementedError(
+            'codeword of %d bits for index %r of column %d: the device '
+            'packer takes at most %d' % (len(word), index, j,
+                                         jpeg.MAX_CODE_BITS))
+      if not 0 <= index < kmax:
+        raise ValueError('index %r of column %d falls outside [0, %d)'
+                         % (index, j, kmax))
+      code[j, index] = int(word, 2) if word else 0
+      length[j, index] = len(word)
+  return code, length
+
+
+# ---------------------------------------------------------------- device side
+def _indices(indices):
+  indices = vtc_hip.require_device_tensor(indices, 'indices', torch.int32)
+  if indices.dim() == 1:
+    indices = indices[:, None]
+  if indices.dim() != 2 or indices.numel() == 0:
+    raise ValueError('indices must be (b, m), got shape %s'
+                     % (tuple(indices.shape),))
+  return indices.contiguous()
+
+
+class _DeviceTables(object):
+  def __init__(self, tables, m, device):
+    tables = list(tables)
+    if len(tables) != m:
+      raise ValueError('%d tables for %d columns' % (len(tables), m))
+    if m > MAX_COLUMNS:
+      raise NotImplementedError('m = %d, at most %d' % (m, MAX_COLUMNS))
+    self.kmax = tables_kmax(tables)
+    if self.kmax > MAX_SYMBOLS:
+      raise NotImplementedError('kmax = %d, at most %d'
+                                % (self.kmax, MAX_SYMBOLS))
+    code, length = index_table_arrays(tables, self.kmax)
+    # uint64 as int64 bits: torch moves bytes
+    self.code = torch.from_numpy(code.view(np.int64)).to(device)
+    self.len = torch.from_numpy(length).to(device)
+
+
+def _raise_status(indices, status, what):
+  uncodable, first, dropped = status.tolist()
+  if uncodable:
+    row, column = divmod(first - 1, indices.shape[1])
+    raise KeyError('%s: column %d has no codeword for index %d (row %d); %d '
+                   'such entries' % (what, column, int(indices[row, column]),
+                                     row, uncodable))
+  if dropped:
+    raise ValueError('%s: %d stream bits outside the output' % (what, dropped))
+
+
+def _bits(lib, indices, tables, status):
+  b, m = indices.shape
+  device = indices.device
+  row_bits = torch.empty(b, dtype=torch.int32, device=device)
+  column_bits = torch.empty(m, dtype=torch.int64, device=device)
+  vtc_hip.check(lib.vtc_index_code_bits(
+      vtc_hip.ptr(indices), b, m, vtc_hip.ptr(tables.len), tables.kmax,
+      vtc_hip.ptr(row_bits), vtc_hip.ptr(column_bits), vtc_hip.ptr(status),
+      vtc_hip.current_stream(device)), 'vtc_index_code_bits')
+  return row_bits, column_bits
+
+
+def index_code_bits(indices, tables):
+  """(row_bits int32 [b], column_bits int64 [m]) device tensors: the length of
+  every row's stream, sum(len(tables[j][indices[r, j]])), and the same
+  lengths summed down each column.  One host read (the status).  An index its
+  column's table lacks (the -1 of a NaN code among them) raises KeyError
+  naming the column and the index."""
+  lib = vtc_hip.load_library()
+  indices = _indices(indices)
+  tables = _DeviceTables(tables, indices.shape[1], indices.device)
+  status = torch.empty(3, dtype=torch.int64, device=indices.device)
+  out = _bits(lib, indices, tables, status)
+  _raise_status(indices, status, 'index_code_bits')
+  return out
+
+
+def pack_index_streams(indices, tables):
+  """(packed, offsets): the streams of all rows back to back in one uint8
+  device tensor, most significant bit first (the last byte zero-padded), and
+  the (b + 1,) int64 device tensor of the bit at which each row's stream
+  starts, the total last -- the return shapes of jpeg.pack_streams.  Row r's
+  stream is ''.join(tables[j][indices[r, j]] for j in range(m))."""
+  lib = vtc_hip.load_library()
+  indices = _indices(indices)
+  b, m = indices.shape
+  device = indices.device
+  tables = _DeviceTables(tables, m, device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  row_bits, _ = _bits(lib, indices, tables, status)
+  _raise_status(indices, status, 'pack_index_streams')
+  offsets = jpeg.bit_offsets(row_bits)
+  total = int(offsets[b])
+  packed = torch.empty(max(1, -(-total // 8)), dtype=torch.uint8,
+                       device=device)
+  vtc_hip.check(lib.vtc_index_code_pack(
+      vtc_hip.ptr(indices), b, m, vtc_hip.ptr(tables.code),
+      vtc_hip.ptr(tables.len), tables.kmax, vtc_hip.ptr(offsets),
+      vtc_hip.ptr(packed), packed.numel(), vtc_hip.ptr(status),
+      vtc_hip.current_stream(device)), 'vtc_index_code_pack')
+  _raise_status(indices, status, 'pack_index_streams')
+  return packed, offsets

@@ -35,6 +35,12 @@ float64), so that a fit costs one device-to-host copy.
 The vector quantiser of the experiment's Mod2 / Mod3 variants lives in
 utils.vector_quantization (include/vtc_vq.h), a superset of
 this module: `from utils import vector_quantization as quantization`.
+
+The rate of a point is the cost of the JPEG source code, the empirical entropy
+of the indices (the default of the baseline and Mod entries) or, with
+source_code='huffman', the bits of the indices under Huffman tables that may
+have been trained on other data (utils.index_coding, include/vtc_index_code.h,
+DESIGN.md 4.17).
 """
 import ctypes
 
@@ -370,7 +376,13 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   (huff_table_ac, huff_table_dc), trained on these indices when None.  A
   column without a zero codeword raises ValueError.  'entropy': the sum over
   the columns of the empirical entropy of the indices (entropy_bits); tables
-  is returned as it came.
+  is returned as it came.  'huffman': every column's indices under a Huffman
+  table of its own (utils.index_coding, include/vtc_index_code.h); `tables` is
+  a list of s dicts {index: codeword}, trained on these indices when None
+  (index_huffman_tables of their counts: every index below the column's k is
+  codable, seen or not), and the rate is the total of index_code_bits, the
+  bits a decoder would read.  With tables trained on other data this is an
+  out-of-sample rate, which no entropy figure of the data itself gives.
 
   Returns (rate in bits per pixel, distortion, tables).  distortion is
   {'pSNR': utils.plotting.compute_pSNR(patches, reconstruction)}; with
@@ -379,8 +391,8 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   'SSIM'} of the images, with the patch figure under 'pSNR_patches'.
   """
   from utils import jpeg
-  if source_code not in ('jpeg', 'entropy'):
-    raise ValueError("source_code must be 'jpeg' or 'entropy'")
+  if source_code not in ('jpeg', 'entropy', 'huffman'):
+    raise ValueError("source_code must be 'jpeg', 'entropy' or 'huffman'")
   codes = _codes(codes)
   patches = _codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
@@ -406,6 +418,12 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
       tables = jpeg.tables_from_counts(*jpeg.symbol_counts(levels))
     bits = jpeg.stream_bits(levels, tables[0], tables[1])
     total_bits = int(jpeg.bit_offsets(bits)[-1])
+  elif source_code == 'huffman':
+    if int(status) != 0:   # before the coder meets their index -1
+      raise ValueError('compute_RD_point: the codes hold NaN')
+    total_bits, tables = _huffman_bits(
+        indices, tables, lambda: (index_counts(indices, pair[0].shape[1]),
+                                  pair[1]))
   else:
     total_bits = entropy_bits(index_counts(indices, pair[0].shape[1]))
   if int(status) != 0:
@@ -413,6 +431,28 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   rate = total_bits / float(patches.numel())
   return rate, _distortion(patches, reconstruction,
                            fullimg_reshape_params), tables
+
+
+def _huffman_bits(indices, tables, counts_and_k):
+  """(total bits of the (b, m) indices under `tables`, the tables): a list of
+  m dicts, trained on counts_and_k() = (counts (m, kmax), k [m]) when None."""
+  from utils import index_coding
+  if tables is None:
+    tables = index_coding.index_huffman_tables(*counts_and_k())
+  _, column_bits = index_coding.index_code_bits(indices, tables)
+  return int(column_bits.sum()), tables
+
+
+def _check_source_code(source_code):
+  if source_code not in ('entropy', 'huffman'):
+    raise ValueError("source_code must be 'entropy' or 'huffman'")
+
+
+def _need_tables(who, *tables):
+  if any(table is None for table in tables):
+    raise ValueError("%s: source_code='huffman' with precomputed codebooks "
+                     'needs the Huffman tables of the training call as well'
+                     % who)
 
 
 def _uniform_for(codes, binwidths, quant_multiplier):
@@ -454,24 +494,40 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
                               binwidths=None, precomputed_codebook=None,
                               precomputed_huff_tab1=None,
                               precomputed_huff_tab2=None,
-                              fullimg_reshape_params=None):
+                              fullimg_reshape_params=None,
+                              source_code='entropy'):
   """The experiment's baseline_compute_RD_point: uniform codebooks with bins
-  of binwidths * quant_multiplier, every column coded at the empirical entropy
-  of its indices.  The return slots are those of the experiment, (rate,
-  distortion, codebook, huff_tab1, huff_tab2) from the training call and
-  (rate, distortion) from a call with precomputed_codebook; the two table
-  slots differ: an entropy figure needs no table, so they are None (and the
-  precomputed_huff_tab* arguments are accepted and unused).  On test data the
-  rate is therefore the entropy of the test indices, not the cost of a code
-  trained elsewhere."""
+  of binwidths * quant_multiplier.  The return slots are those of the
+  experiment, (rate, distortion, codebook, huff_tab1, huff_tab2) from the
+  training call and (rate, distortion) from a call with precomputed_codebook.
+
+  source_code 'entropy' (the default): every column is coded at the empirical
+  entropy of its indices.  An entropy figure needs no table, so the two table
+  slots are None (and the precomputed_huff_tab* arguments are accepted and
+  unused); on test data the rate is then the entropy of the test indices, not
+  the cost of a code trained elsewhere.
+
+  source_code 'huffman': every column's indices under a Huffman table of its
+  own (compute_RD_point).  The experiment's missing module never said what its
+  table slots held; here the training call returns huff_tab1 = the list of s
+  scalar tables and huff_tab2 = None, and a test call (precomputed_codebook
+  and precomputed_huff_tab1) measures the bits of the test indices under the
+  trained tables.  Precomputed codebooks without the tables raise
+  ValueError."""
+  _check_source_code(source_code)
   training = precomputed_codebook is None
+  if source_code == 'huffman' and not training:
+    _need_tables('baseline_compute_RD_point', precomputed_huff_tab1)
   codebook = (_uniform_for(codes, binwidths, quant_multiplier) if training
               else precomputed_codebook)
-  rate, distortion, _ = compute_RD_point(
-      codes, patches, dictionary, codebook, source_code='entropy',
+  rate, distortion, tables = compute_RD_point(
+      codes, patches, dictionary, codebook, source_code=source_code,
+      tables=(precomputed_huff_tab1 if source_code == 'huffman' and
+              not training else None),
       fullimg_reshape_params=fullimg_reshape_params)
   if training:
-    return rate, distortion, codebook, None, None
+    return (rate, distortion, codebook,
+            tables if source_code == 'huffman' else None, None)
   return rate, distortion
 
 
@@ -480,17 +536,25 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
                           precomputed_codebook_lengths=None,
                           precomputed_huff_tab1=None,
                           fullimg_reshape_params=None, max_iterations=50,
-                          epsilon=1e-5):
+                          epsilon=1e-5, source_code='entropy'):
   """The experiment's Mod1_compute_RD_point: entropy-constrained scalar Lloyd
   quantisers (scalar_lloyd) started from uniform codebooks of bin width
   init_binwidths, with lagrange_mult = quant_multiplier; the rate is the
   empirical entropy of the indices.  Training call: returns (rate,
   distortion, codebook, codeword lengths, huff_tab1) where codebook is the
   dictionary of scalar_lloyd, the lengths its 'lengths' and the last slot,
-  the experiment's Huffman table, is None here (see baseline_compute_RD_point).
+  the experiment's Huffman table, is None (see baseline_compute_RD_point).
   Test call (precomputed_codebook and precomputed_codebook_lengths): returns
-  (rate, distortion)."""
+  (rate, distortion).
+
+  With source_code='huffman' the rate is the bits of the indices under one
+  Huffman table per column, huff_tab1 is the list of those s tables, and a
+  test call takes them back as precomputed_huff_tab1 (ValueError without
+  them), as baseline_compute_RD_point does."""
+  _check_source_code(source_code)
   training = precomputed_codebook is None
+  if source_code == 'huffman' and not training:
+    _need_tables('Mod1_compute_RD_point', precomputed_huff_tab1)
   if training:
     fit = scalar_lloyd(codes, _uniform_for(codes, init_binwidths, 1.0),
                        lagrange_mult=quant_multiplier,
@@ -498,10 +562,13 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
     codebook, lengths = fit, fit['lengths']
   else:
     codebook, lengths = precomputed_codebook, precomputed_codebook_lengths
-  rate, distortion, _ = compute_RD_point(
+  rate, distortion, tables = compute_RD_point(
       codes, patches, dictionary, codebook, lengths=lengths,
-      lagrange_mult=quant_multiplier, source_code='entropy',
+      lagrange_mult=quant_multiplier, source_code=source_code,
+      tables=(precomputed_huff_tab1 if source_code == 'huffman' and
+              not training else None),
       fullimg_reshape_params=fullimg_reshape_params)
   if training:
-    return rate, distortion, codebook, lengths, None
+    return (rate, distortion, codebook, lengths,
+            tables if source_code == 'huffman' else None)
   return rate, distortion

@@ -294,7 +294,8 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                            scal_codebooks, vec_clust, vec_codebook,
                            scal_lengths=None, scal_lagrange_mult=0.0,
                            vec_lengths=None, vec_lagrange_mult=0.0,
-                           fullimg_reshape_params=None):
+                           fullimg_reshape_params=None, source_code='entropy',
+                           tables=None):
   """One rate-distortion point of codes quantised in two parts.
 
   codes : (b, s) float32 device tensor; patches : (b, n); dictionary : (s, n),
@@ -310,7 +311,17 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   Returns (rate, distortion): the rate is (the sum over the scalar columns of
   the empirical entropy of their indices + the entropy of the vector indices)
   / patches.numel() in bits per pixel (entropy_bits); reconstruction and
-  distortion are those of compute_RD_point."""
+  distortion are those of compute_RD_point.
+
+  source_code 'huffman': the scalar indices and the vector index form one
+  (b, len(scal_clusts) + 1) index array, scalars first in scal_clusts order,
+  the vector column last, and every column is coded under a Huffman table of
+  its own (utils.index_coding; the tables are padded to the larger kmax).
+  `tables` = (scalar_tables, vector_table): a list of len(scal_clusts) dicts
+  and one dict, trained on these indices when None.  The rate is the total of
+  index_code_bits / patches.numel(), and a third value is returned: the
+  tables."""
+  _scalar._check_source_code(source_code)
   codes = _scalar._codes(codes)
   patches = _scalar._codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
@@ -342,15 +353,32 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   dequantized.index_copy_(1, scal_at, scal_deq)
   dequantized.index_copy_(1, vec_at, vec_deq)
   reconstruction = _scalar._reconstruct(dequantized, dictionary)
-  total_bits = (
-      entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
-      entropy_bits(vector_index_counts(vec_indices,
-                                       vec_values.shape[0])[None, :]))
   if int(scal_status) != 0 or int(vec_status) != 0:
     raise ValueError('compute_RD_point_mixed: the codes hold NaN')
+  if source_code == 'huffman':
+    from utils import index_coding
+    if tables is None:
+      tables = (
+          index_coding.index_huffman_tables(
+              index_counts(scal_indices, scal_pair[0].shape[1]), scal_pair[1]),
+          index_coding.index_huffman_tables(
+              vector_index_counts(vec_indices, vec_values.shape[0]),
+              vec_k)[0])
+    scalar_tables, vector_table = tables
+    total_bits, _ = _scalar._huffman_bits(
+        torch.cat([scal_indices, vec_indices[:, None]], 1),
+        list(scalar_tables) + [vector_table], None)
+  else:
+    total_bits = (
+        entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
+        entropy_bits(vector_index_counts(vec_indices,
+                                         vec_values.shape[0])[None, :]))
   rate = total_bits / float(patches.numel())
-  return rate, _scalar._distortion(patches, reconstruction,
+  distortion = _scalar._distortion(patches, reconstruction,
                                    fullimg_reshape_params)
+  if source_code == 'huffman':
+    return rate, distortion, (list(scalar_tables), vector_table)
+  return rate, distortion
 
 
 def _gathered(codes, cluster):
@@ -369,6 +397,22 @@ def _fit_vector_part(codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
                       max_iterations=max_iterations, epsilon=epsilon)
 
 
+def _mixed_point(who, training, source_code, huff_tab1, huff_tab2, *args,
+                 **kwargs):
+  """compute_RD_point_mixed for Mod2 / Mod3: (rate, distortion, huff_tab1,
+  huff_tab2), the two tables None under 'entropy'."""
+  _scalar._check_source_code(source_code)
+  if source_code != 'huffman':
+    return compute_RD_point_mixed(*args, **kwargs) + (None, None)
+  tables = None
+  if not training:
+    _scalar._need_tables(who, huff_tab1, huff_tab2)
+    tables = (huff_tab1, huff_tab2)
+  rate, distortion, tables = compute_RD_point_mixed(
+      *args, source_code='huffman', tables=tables, **kwargs)
+  return rate, distortion, tables[0], tables[1]
+
+
 def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           scal_quant_multiplier=1.0, scal_binwidths=None,
                           vec_quant_multiplier=1.0, vec_init_num_bins=4096,
@@ -379,7 +423,7 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab2=None,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
-                          epsilon=1e-5):
+                          epsilon=1e-5, source_code='entropy'):
   """The experiment's Mod2_compute_RD_point, with (b, s) codes (module
   docstring): the columns scal_clusts get uniform scalar codebooks of bin
   width scal_binwidths * scal_quant_multiplier (as in
@@ -395,7 +439,16 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   baseline_compute_RD_point's docstring gives (and the precomputed_huff_tab*
   arguments are accepted and unused).  Test call (precomputed_scal_codebook,
   precomputed_vec_codebook, precomputed_vec_codebook_lengths): returns
-  (rate, distortion)."""
+  (rate, distortion).
+
+  With source_code='huffman' every index stream is coded under a Huffman
+  table of its own instead (compute_RD_point_mixed).  The experiment's missing
+  module never said what its three table slots held; here the training call
+  returns huff_tab1 = the list of len(scal_clusts) scalar tables, huff_tab2 =
+  the vector table, huff_tab3 = None, and a test call takes the first two back
+  as precomputed_huff_tab1 and precomputed_huff_tab2 and measures the bits of
+  the test indices under them.  Precomputed codebooks without both tables
+  raise ValueError."""
   training = precomputed_scal_codebook is None
   if training:
     scal_cbook = _scalar._uniform_for(_gathered(codes, scal_clusts),
@@ -407,14 +460,16 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
     scal_cbook, vec_cbook, vec_cw_len = (precomputed_scal_codebook,
                                          precomputed_vec_codebook,
                                          precomputed_vec_codebook_lengths)
-  rate, distortion = compute_RD_point_mixed(
+  rate, distortion, huff_tab1, huff_tab2 = _mixed_point(
+      'Mod2_compute_RD_point', training, source_code, precomputed_huff_tab1,
+      precomputed_huff_tab2,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, vec_lengths=vec_cw_len,
       vec_lagrange_mult=vec_quant_multiplier,
       fullimg_reshape_params=fullimg_reshape_params)
   if training:
-    return (rate, distortion, scal_cbook, vec_cbook, vec_cw_len, None, None,
-            None)
+    return (rate, distortion, scal_cbook, vec_cbook, vec_cw_len, huff_tab1,
+            huff_tab2, None)
   return rate, distortion
 
 
@@ -428,7 +483,7 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab2=None,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
-                          epsilon=1e-5):
+                          epsilon=1e-5, source_code='entropy'):
   """The experiment's Mod3_compute_RD_point: Mod2_compute_RD_point with
   entropy-constrained scalar quantisers, scalar_lloyd from uniform codebooks
   of bin width scal_binwidths with lagrange_mult = scal_quant_multiplier (as
@@ -436,7 +491,7 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   scalar multiplier again, so the returned scal_cbook is scalar_lloyd's
   dictionary with one more key, 'lagrange_mult', and a test call assigns with
   that value and the dictionary's 'lengths'.  Returns as Mod2_compute_RD_point
-  does."""
+  does, source_code='huffman' and its table slots included."""
   training = precomputed_scal_codebook is None
   if training:
     scal_codes = _gathered(codes, scal_clusts)
@@ -452,13 +507,15 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
     scal_cbook, vec_cbook, vec_cw_len = (precomputed_scal_codebook,
                                          precomputed_vec_codebook,
                                          precomputed_vec_codebook_lengths)
-  rate, distortion = compute_RD_point_mixed(
+  rate, distortion, huff_tab1, huff_tab2 = _mixed_point(
+      'Mod3_compute_RD_point', training, source_code, precomputed_huff_tab1,
+      precomputed_huff_tab2,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, scal_lengths=scal_cbook['lengths'],
       scal_lagrange_mult=scal_cbook['lagrange_mult'], vec_lengths=vec_cw_len,
       vec_lagrange_mult=vec_quant_multiplier,
       fullimg_reshape_params=fullimg_reshape_params)
   if training:
-    return (rate, distortion, scal_cbook, vec_cbook, vec_cw_len, None, None,
-            None)
+    return (rate, distortion, scal_cbook, vec_cbook, vec_cw_len, huff_tab1,
+            huff_tab2, None)
   return rate, distortion

@@ -1,8 +1,8 @@
 """
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
-include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h and
-include/vtc_vq.h).
+include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h,
+include/vtc_vq.h and include/vtc_index_code.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -295,6 +295,21 @@ VQ_SIGNATURES = {
     'vtc_vq_index_counts': (_i32, [_vp, _i64, _i32, _vp, _vp]),
 }
 
+INDEX_CODE_ABI_VERSION = 1   # VTC_INDEX_CODE_ABI_VERSION of vtc_index_code.h
+INDEX_CODE_ABSENT = 255
+INDEX_CODE_MAX_COLUMNS, INDEX_CODE_MAX_SYMBOLS = 4096, 4096
+
+# The ninth header, include/vtc_index_code.h (same library): prefix codes for
+# quantiser indices, bits per row and per column, packed streams.  Again a
+# table of its own.
+INDEX_CODE_SIGNATURES = {
+    'vtc_index_code_abi_version': (_i32, []),
+    'vtc_index_code_bits': (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp,
+                                   _vp]),
+    'vtc_index_code_pack': (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp,
+                                   _i64, _vp, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -313,7 +328,7 @@ def load_library():
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
-                QUANT_SIGNATURES, VQ_SIGNATURES):
+                QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -334,6 +349,8 @@ def load_library():
     raise ImportError('libvtc_hip.so quant ABI version mismatch')
   if lib.vtc_vq_abi_version() != VQ_ABI_VERSION:
     raise ImportError('libvtc_hip.so vector quantiser ABI version mismatch')
+  if lib.vtc_index_code_abi_version() != INDEX_CODE_ABI_VERSION:
+    raise ImportError('libvtc_hip.so index code ABI version mismatch')
   _lib = lib
   return lib
 
