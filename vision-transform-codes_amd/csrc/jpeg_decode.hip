@@ -25,6 +25,7 @@
 #include <limits.h>
 
 #include "../../include/vtc_decode.h"
+#include "bitstream.h"
 #include "common.h"
 
 namespace vtc {
@@ -38,8 +39,6 @@ constexpr int kEob = 0x00, kZrl = 0xF0;
 constexpr int kLutBits = 10;
 constexpr int kLutSize = 1 << kLutBits;
 constexpr int kMaxCodeBits = 64;
-
-typedef unsigned long long u64;
 
 // meta word of a codeword: length << 9 | symbol id (ids below 272, lengths
 // 1..64); 0 is no codeword.
@@ -161,69 +160,7 @@ __global__ void unpack_end_kernel(u64* status) {
   if (status[1] == ULLONG_MAX) status[1] = 0;
 }
 
-// ---- the bit reader of one lane ---------------------------------------------
-// `win` holds the next `have` stream bits from `pos` on, left-aligned, zeros
-// behind them.  A byte is loaded only when its index is below `nbytes` and
-// its first bit below `end`; what a caller may use of the window is avail():
-// the bits that are loaded AND belong to the row.
-struct BitReader {
-  const uint8_t* bytes;
-  int64_t nbytes;   // packed_bytes
-  int64_t end;      // the row's end, at most 8 * nbytes
-  int64_t pos;      // >= 0
-  int64_t next;     // index of the next byte to load
-  u64 win;
-  int have;
-
-  __device__ __forceinline__ bool loadable() const {
-    return next < nbytes && next * 8 < end;
-  }
-  __device__ __forceinline__ void seek(int64_t to) {
-    pos = to;
-    next = to >> 3;
-    win = 0;
-    have = 0;
-    const int skip = (int)(to & 7);
-    if (skip && loadable()) {   // the bits before `to` fall off the top
-      win = (u64)bytes[next] << (56 + skip);
-      have = 8 - skip;
-      ++next;
-    }
-  }
-  __device__ __forceinline__ void refill() {
-    while (have <= 56 && loadable()) {
-      win |= (u64)bytes[next] << (56 - have);
-      have += 8;
-      ++next;
-    }
-  }
-  // After refill(): the 64 bits from pos on.  refill() stops at 57..64 bits;
-  // the top of one more byte completes them, without being consumed.
-  __device__ __forceinline__ u64 window64() const {
-    if (have >= 57 && have < 64 && loadable())
-      return win | (u64)bytes[next] >> (have - 56);
-    return win;
-  }
-  __device__ __forceinline__ int64_t avail() const {
-    const int64_t left = end - pos;
-    return left < have ? left : have;
-  }
-  // the same for window64()
-  __device__ __forceinline__ int64_t avail64() const {
-    const int64_t left = end - pos;
-    const int loaded = have >= 57 && have < 64 && loadable() ? 64 : have;
-    return left < loaded ? left : loaded;
-  }
-  __device__ __forceinline__ void consume(int n) {
-    if (n < have) {
-      win <<= n;
-      have -= n;
-      pos += n;
-    } else {
-      seek(pos + n);
-    }
-  }
-};
+// BitReader, the bit reader of one lane: bitstream.h
 
 // The codeword the window starts with, as a meta word; 0 when none does.
 // lut, code, meta: one table's arrays in LDS; n: its codewords.

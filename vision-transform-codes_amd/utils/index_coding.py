@@ -15,11 +15,15 @@ charges the test codes what those tables cost.  Here
   pack_index_streams     indices (b, m), tables -> (packed, offsets), the
                          layout of jpeg.pack_streams: jpeg.stream_as_str reads
                          a row back as a string of '0' and '1'
+  unpack_index_streams   (packed, offsets), tables -> indices (b, m): the
+                         inverse of pack_index_streams
+  parse_index_stream     one string of '0' / '1', tables -> its m indices
 
 The per-entry work runs in the kernels of csrc/index_code.hip behind
-include/vtc_index_code.h.  Indices are (b, m) int32 device
-tensors: m index streams ("columns") per row, each with a table of its own,
-{int index: str of '0' / '1'}.  There is no decoder yet.
+include/vtc_index_code.h and, for the way back, of
+csrc/index_decode.hip behind include/vtc_index_decode.h.
+Indices are (b, m) int32 device tensors: m index streams ("columns") per row,
+each with a table of its own, {int index: str of '0' / '1'}.
 """
 import numpy as np
 import torch
@@ -203,3 +207,88 @@ def pack_index_streams(indices, tables):
       vtc_hip.current_stream(device)), 'vtc_index_code_pack')
   _raise_status(indices, status, 'pack_index_streams')
   return packed, offsets
+
+
+# ------------------------------------------------------------------ decoding
+def unpack_index_streams(packed, offsets, tables, exact=True):
+  """indices (b, m) int32 device tensor from what pack_index_streams returns:
+  packed a uint8 device tensor, offsets the (b + 1,) int64 device tensor of the
+  bit at which each row's stream starts, the total last; m = len(tables).  Row
+  r reads one codeword per column from bit offsets[r] on and may use the bits
+  below offsets[r + 1].
+
+  ValueError for a column whose table is not prefix-free (before any device
+  work; {0: ''} alone is fine), for malformed rows (their number, the first one
+  and its first undecoded column named; include/vtc_index_decode.h lists what
+  makes a row malformed) and, with exact=True, for rows that leave bits of
+  their span offsets[r + 1] - offsets[r] unread.  NotImplementedError for a
+  codeword of more than 64 bits, VtcHipError for a CPU tensor.  One host read
+  in all."""
+  tables = list(tables)
+  for j, table in enumerate(tables):
+    try:
+      jpeg.check_prefix_free(table)
+    except ValueError as e:
+      raise ValueError('column %d: %s' % (j, e))
+  packed = vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
+  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
+  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] < 2:
+    raise ValueError('packed must be (bytes,) and offsets (b + 1,), got '
+                     'shapes %s and %s' % (tuple(packed.shape),
+                                           tuple(offsets.shape)))
+  lib = vtc_hip.load_library()
+  packed, offsets = packed.contiguous(), offsets.contiguous()
+  device = packed.device
+  b, m = offsets.shape[0] - 1, len(tables)
+  tables = _DeviceTables(tables, m, device)
+  indices = torch.empty((b, m), dtype=torch.int32, device=device)
+  row_bits = torch.empty(b, dtype=torch.int32, device=device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  ws = vtc_hip.workspace(
+      lib.vtc_index_code_unpack_workspace_bytes(m, tables.kmax), device)
+  # a tensor without elements has a null data pointer; the call wants one
+  # that is not null and never reads it when there are no bytes
+  bits_from = packed if packed.numel() else ws
+  vtc_hip.check(lib.vtc_index_code_unpack(
+      vtc_hip.ptr(bits_from), packed.numel(), vtc_hip.ptr(offsets), b, m,
+      vtc_hip.ptr(tables.code), vtc_hip.ptr(tables.len), tables.kmax,
+      vtc_hip.ptr(indices), vtc_hip.ptr(row_bits), vtc_hip.ptr(status),
+      vtc_hip.ptr(ws), ws.numel(), vtc_hip.current_stream(device)),
+                'vtc_index_code_unpack')
+  # what the message needs, gathered on the device for the one host read: the
+  # first malformed row's first undecoded column, and the rows that did not
+  # use up their span (tensor plumbing, b elements)
+  first_row = (status[1] - 1).clamp(min=0)
+  undecoded = (indices.index_select(0, first_row.reshape(1))[0] < 0)
+  column = undecoded.to(torch.int32).argmax().to(torch.int64)
+  loose = row_bits.to(torch.int64) != offsets[1:] - offsets[:-1]
+  report = torch.stack([status[0], status[1], status[2], column,
+                        loose.sum(), loose.to(torch.int32).argmax()])
+  malformed, first, clash, column, loose, first_loose = report.tolist()
+  if clash:   # the host check above saw the same tables
+    raise ValueError('not a prefix-free table: column %d, index %d'
+                     % divmod(clash - 1, tables.kmax))
+  if malformed:
+    raise ValueError('unpack_index_streams: %d malformed rows of %d, the '
+                     'first is row %d, undecoded from column %d on'
+                     % (malformed, b, first - 1, column))
+  if exact and loose:
+    raise ValueError('unpack_index_streams: %d rows of %d do not use up their '
+                     'span of bits, the first is row %d'
+                     % (loose, b, first_loose))
+  return indices
+
+
+def parse_index_stream(stream, tables):
+  """The inverse of ''.join(tables[j][i] for j, i in enumerate(indices)) for
+  one row: the list of m ints whose stream is the string `stream` of '0' and
+  '1'.  Through the batch path with b = 1, on the current HIP device."""
+  if not isinstance(stream, str) or set(stream) - set('01'):
+    raise TypeError("stream must be a str of '0' and '1'")
+  device = torch.device('cuda')
+  bits = np.frombuffer(stream.encode('ascii'), dtype=np.uint8) - ord('0')
+  host = np.packbits(bits) if len(stream) else np.zeros(1, dtype=np.uint8)
+  ends = np.array([0, len(stream)], dtype=np.int64)
+  indices = unpack_index_streams(torch.from_numpy(host).to(device),
+                                 torch.from_numpy(ends).to(device), tables)
+  return [int(i) for i in indices[0].tolist()]

@@ -363,7 +363,7 @@ def _distortion(patches, reconstruction, fullimg_reshape_params):
 
 def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
                      lagrange_mult=0.0, source_code='jpeg', tables=None,
-                     fullimg_reshape_params=None):
+                     fullimg_reshape_params=None, from_stream=False):
   """One rate-distortion point of quantised codes.
 
   codes : (b, s) float32 device tensor; patches : (b, n) float32 device
@@ -384,6 +384,12 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   bits a decoder would read.  With tables trained on other data this is an
   out-of-sample rate, which no entropy figure of the data itself gives.
 
+  from_stream (source_code 'huffman' only, ValueError otherwise): the indices
+  are packed with index_coding.pack_index_streams and read back by
+  decode_codes; reconstruction and distortion are those of the decoded codes
+  and the rate is the streams' total bits / patches.numel().  What is charged
+  has then been decoded, and what is measured has been through the bytes.
+
   Returns (rate in bits per pixel, distortion, tables).  distortion is
   {'pSNR': utils.plotting.compute_pSNR(patches, reconstruction)}; with
   fullimg_reshape_params = {'patch_dim', 'patch_positions'} both are
@@ -393,6 +399,7 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   from utils import jpeg
   if source_code not in ('jpeg', 'entropy', 'huffman'):
     raise ValueError("source_code must be 'jpeg', 'entropy' or 'huffman'")
+  _check_from_stream(from_stream, source_code)
   codes = _codes(codes)
   patches = _codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
@@ -411,7 +418,8 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
                        'needs one' % missing[0])
   indices, dequantized, status = _assign(codes, pair, lengths, lagrange_mult,
                                          True)
-  reconstruction = _reconstruct(dequantized, dictionary)
+  if not from_stream:
+    reconstruction = _reconstruct(dequantized, dictionary)
   if source_code == 'jpeg':
     levels = jpeg._relative_levels(indices, zero)
     if tables is None:
@@ -421,9 +429,14 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   elif source_code == 'huffman':
     if int(status) != 0:   # before the coder meets their index -1
       raise ValueError('compute_RD_point: the codes hold NaN')
-    total_bits, tables = _huffman_bits(
-        indices, tables, lambda: (index_counts(indices, pair[0].shape[1]),
-                                  pair[1]))
+    counts_and_k = lambda: (index_counts(indices, pair[0].shape[1]), pair[1])
+    if from_stream:
+      total_bits, tables, streams = _huffman_streams(indices, tables,
+                                                     counts_and_k)
+      reconstruction = _reconstruct(decode_codes(*streams, tables, pair),
+                                    dictionary)
+    else:
+      total_bits, tables = _huffman_bits(indices, tables, counts_and_k)
   else:
     total_bits = entropy_bits(index_counts(indices, pair[0].shape[1]))
   if int(status) != 0:
@@ -441,6 +454,33 @@ def _huffman_bits(indices, tables, counts_and_k):
     tables = index_coding.index_huffman_tables(*counts_and_k())
   _, column_bits = index_coding.index_code_bits(indices, tables)
   return int(column_bits.sum()), tables
+
+
+def _huffman_streams(indices, tables, counts_and_k):
+  """_huffman_bits from the packed streams: (their total bits, the tables,
+  (packed, offsets))."""
+  from utils import index_coding
+  if tables is None:
+    tables = index_coding.index_huffman_tables(*counts_and_k())
+  packed, offsets = index_coding.pack_index_streams(indices, tables)
+  return int(offsets[-1]), tables, (packed, offsets)
+
+
+def _check_from_stream(from_stream, source_code):
+  if from_stream and source_code != 'huffman':
+    raise ValueError("from_stream=True needs source_code='huffman': only "
+                     'that source code writes streams of indices')
+
+
+def decode_codes(packed, offsets, tables, codebooks):
+  """The (b, s) float32 dequantised codes whose index streams are in (packed,
+  offsets), what index_coding.pack_index_streams returns for the (b, s)
+  indices of `assign`: index_coding.unpack_index_streams under the s tables,
+  then dequantize_assignments with the codebooks.  One host read (the
+  decoder's status)."""
+  from utils import index_coding
+  return dequantize_assignments(
+      index_coding.unpack_index_streams(packed, offsets, tables), codebooks)
 
 
 def _check_source_code(source_code):
@@ -495,7 +535,7 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
                               precomputed_huff_tab1=None,
                               precomputed_huff_tab2=None,
                               fullimg_reshape_params=None,
-                              source_code='entropy'):
+                              source_code='entropy', from_stream=False):
   """The experiment's baseline_compute_RD_point: uniform codebooks with bins
   of binwidths * quant_multiplier.  The return slots are those of the
   experiment, (rate, distortion, codebook, huff_tab1, huff_tab2) from the
@@ -513,8 +553,9 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   scalar tables and huff_tab2 = None, and a test call (precomputed_codebook
   and precomputed_huff_tab1) measures the bits of the test indices under the
   trained tables.  Precomputed codebooks without the tables raise
-  ValueError."""
+  ValueError.  from_stream: as in compute_RD_point."""
   _check_source_code(source_code)
+  _check_from_stream(from_stream, source_code)
   training = precomputed_codebook is None
   if source_code == 'huffman' and not training:
     _need_tables('baseline_compute_RD_point', precomputed_huff_tab1)
@@ -524,7 +565,7 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
       codes, patches, dictionary, codebook, source_code=source_code,
       tables=(precomputed_huff_tab1 if source_code == 'huffman' and
               not training else None),
-      fullimg_reshape_params=fullimg_reshape_params)
+      fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream)
   if training:
     return (rate, distortion, codebook,
             tables if source_code == 'huffman' else None, None)
@@ -536,7 +577,8 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
                           precomputed_codebook_lengths=None,
                           precomputed_huff_tab1=None,
                           fullimg_reshape_params=None, max_iterations=50,
-                          epsilon=1e-5, source_code='entropy'):
+                          epsilon=1e-5, source_code='entropy',
+                          from_stream=False):
   """The experiment's Mod1_compute_RD_point: entropy-constrained scalar Lloyd
   quantisers (scalar_lloyd) started from uniform codebooks of bin width
   init_binwidths, with lagrange_mult = quant_multiplier; the rate is the
@@ -550,8 +592,9 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   With source_code='huffman' the rate is the bits of the indices under one
   Huffman table per column, huff_tab1 is the list of those s tables, and a
   test call takes them back as precomputed_huff_tab1 (ValueError without
-  them), as baseline_compute_RD_point does."""
+  them), as baseline_compute_RD_point does; from_stream likewise."""
   _check_source_code(source_code)
+  _check_from_stream(from_stream, source_code)
   training = precomputed_codebook is None
   if source_code == 'huffman' and not training:
     _need_tables('Mod1_compute_RD_point', precomputed_huff_tab1)
@@ -567,7 +610,7 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
       lagrange_mult=quant_multiplier, source_code=source_code,
       tables=(precomputed_huff_tab1 if source_code == 'huffman' and
               not training else None),
-      fullimg_reshape_params=fullimg_reshape_params)
+      fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream)
   if training:
     return (rate, distortion, codebook, lengths,
             tables if source_code == 'huffman' else None)

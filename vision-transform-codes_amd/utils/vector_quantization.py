@@ -295,7 +295,7 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                            scal_lengths=None, scal_lagrange_mult=0.0,
                            vec_lengths=None, vec_lagrange_mult=0.0,
                            fullimg_reshape_params=None, source_code='entropy',
-                           tables=None):
+                           tables=None, from_stream=False):
   """One rate-distortion point of codes quantised in two parts.
 
   codes : (b, s) float32 device tensor; patches : (b, n); dictionary : (s, n),
@@ -320,8 +320,14 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   `tables` = (scalar_tables, vector_table): a list of len(scal_clusts) dicts
   and one dict, trained on these indices when None.  The rate is the total of
   index_code_bits / patches.numel(), and a third value is returned: the
-  tables."""
+  tables.
+
+  from_stream (source_code 'huffman' only, ValueError otherwise): that index
+  array is packed with index_coding.pack_index_streams and read back by
+  decode_codes_mixed; reconstruction and distortion are those of the decoded
+  codes and the rate is the streams' total bits / patches.numel()."""
   _scalar._check_source_code(source_code)
+  _scalar._check_from_stream(from_stream, source_code)
   codes = _scalar._codes(codes)
   patches = _scalar._codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
@@ -352,7 +358,8 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   dequantized = torch.zeros((b, s), dtype=torch.float32, device=device)
   dequantized.index_copy_(1, scal_at, scal_deq)
   dequantized.index_copy_(1, vec_at, vec_deq)
-  reconstruction = _scalar._reconstruct(dequantized, dictionary)
+  if not from_stream:
+    reconstruction = _scalar._reconstruct(dequantized, dictionary)
   if int(scal_status) != 0 or int(vec_status) != 0:
     raise ValueError('compute_RD_point_mixed: the codes hold NaN')
   if source_code == 'huffman':
@@ -365,9 +372,16 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
               vector_index_counts(vec_indices, vec_values.shape[0]),
               vec_k)[0])
     scalar_tables, vector_table = tables
-    total_bits, _ = _scalar._huffman_bits(
-        torch.cat([scal_indices, vec_indices[:, None]], 1),
-        list(scalar_tables) + [vector_table], None)
+    streams = torch.cat([scal_indices, vec_indices[:, None]], 1)
+    all_tables = list(scalar_tables) + [vector_table]
+    if from_stream:
+      total_bits, _, (packed, offsets) = _scalar._huffman_streams(
+          streams, all_tables, None)
+      reconstruction = _scalar._reconstruct(
+          decode_codes_mixed(packed, offsets, all_tables, scal, scal_pair, vec,
+                             (vec_values, vec_k), s), dictionary)
+    else:
+      total_bits, _ = _scalar._huffman_bits(streams, all_tables, None)
   else:
     total_bits = (
         entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
@@ -379,6 +393,42 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   if source_code == 'huffman':
     return rate, distortion, (list(scalar_tables), vector_table)
   return rate, distortion
+
+
+def decode_codes_mixed(packed, offsets, tables, scal_clusts, scal_codebooks,
+                       vec_clust, vec_codebook, s):
+  """The (b, s) float32 dequantised codes whose index streams are in (packed,
+  offsets), the layout compute_RD_point_mixed codes: one row per patch, the
+  scalar indices first in scal_clusts order, the vector index last.  `tables`
+  is the list of len(scal_clusts) + 1 tables in that order.
+  index_coding.unpack_index_streams, then quantization.dequantize_assignments
+  into the columns scal_clusts and vector_dequantize into the columns
+  vec_clust; a column in neither cluster is zero.  One host read (the
+  decoder's status)."""
+  from utils import index_coding
+  s = int(s)
+  scal = _cluster(scal_clusts, s, 'scal_clusts')
+  vec = _cluster(vec_clust, s, 'vec_clust')
+  if len(set(scal + vec)) != len(scal) + len(vec):
+    raise ValueError('scal_clusts and vec_clust overlap')
+  tables = list(tables)
+  if len(tables) != len(scal) + 1:
+    raise ValueError('%d tables for %d scalar columns and the vector column'
+                     % (len(tables), len(scal)))
+  indices = index_coding.unpack_index_streams(packed, offsets, tables)
+  device = indices.device
+  scal_deq = _scalar.dequantize_assignments(
+      indices[:, :len(scal)].contiguous(), scal_codebooks)
+  vec_deq = vector_dequantize(indices[:, len(scal)].contiguous(), vec_codebook)
+  if vec_deq.shape[1] != len(vec):
+    raise ValueError('vec_codebook must be (kmax, %d)' % len(vec))
+  codes = torch.zeros((indices.shape[0], s), dtype=torch.float32,
+                      device=device)
+  codes.index_copy_(1, torch.tensor(scal, dtype=torch.int64, device=device),
+                    scal_deq)
+  codes.index_copy_(1, torch.tensor(vec, dtype=torch.int64, device=device),
+                    vec_deq)
+  return codes
 
 
 def _gathered(codes, cluster):
@@ -397,11 +447,12 @@ def _fit_vector_part(codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
                       max_iterations=max_iterations, epsilon=epsilon)
 
 
-def _mixed_point(who, training, source_code, huff_tab1, huff_tab2, *args,
-                 **kwargs):
+def _mixed_point(who, training, source_code, from_stream, huff_tab1,
+                 huff_tab2, *args, **kwargs):
   """compute_RD_point_mixed for Mod2 / Mod3: (rate, distortion, huff_tab1,
   huff_tab2), the two tables None under 'entropy'."""
   _scalar._check_source_code(source_code)
+  _scalar._check_from_stream(from_stream, source_code)
   if source_code != 'huffman':
     return compute_RD_point_mixed(*args, **kwargs) + (None, None)
   tables = None
@@ -409,7 +460,8 @@ def _mixed_point(who, training, source_code, huff_tab1, huff_tab2, *args,
     _scalar._need_tables(who, huff_tab1, huff_tab2)
     tables = (huff_tab1, huff_tab2)
   rate, distortion, tables = compute_RD_point_mixed(
-      *args, source_code='huffman', tables=tables, **kwargs)
+      *args, source_code='huffman', tables=tables, from_stream=from_stream,
+      **kwargs)
   return rate, distortion, tables[0], tables[1]
 
 
@@ -423,7 +475,8 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab2=None,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
-                          epsilon=1e-5, source_code='entropy'):
+                          epsilon=1e-5, source_code='entropy',
+                          from_stream=False):
   """The experiment's Mod2_compute_RD_point, with (b, s) codes (module
   docstring): the columns scal_clusts get uniform scalar codebooks of bin
   width scal_binwidths * scal_quant_multiplier (as in
@@ -448,7 +501,7 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   the vector table, huff_tab3 = None, and a test call takes the first two back
   as precomputed_huff_tab1 and precomputed_huff_tab2 and measures the bits of
   the test indices under them.  Precomputed codebooks without both tables
-  raise ValueError."""
+  raise ValueError.  from_stream is that of compute_RD_point_mixed."""
   training = precomputed_scal_codebook is None
   if training:
     scal_cbook = _scalar._uniform_for(_gathered(codes, scal_clusts),
@@ -461,8 +514,8 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                                          precomputed_vec_codebook,
                                          precomputed_vec_codebook_lengths)
   rate, distortion, huff_tab1, huff_tab2 = _mixed_point(
-      'Mod2_compute_RD_point', training, source_code, precomputed_huff_tab1,
-      precomputed_huff_tab2,
+      'Mod2_compute_RD_point', training, source_code, from_stream,
+      precomputed_huff_tab1, precomputed_huff_tab2,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, vec_lengths=vec_cw_len,
       vec_lagrange_mult=vec_quant_multiplier,
@@ -483,7 +536,8 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab2=None,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
-                          epsilon=1e-5, source_code='entropy'):
+                          epsilon=1e-5, source_code='entropy',
+                          from_stream=False):
   """The experiment's Mod3_compute_RD_point: Mod2_compute_RD_point with
   entropy-constrained scalar quantisers, scalar_lloyd from uniform codebooks
   of bin width scal_binwidths with lagrange_mult = scal_quant_multiplier (as
@@ -491,7 +545,7 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   scalar multiplier again, so the returned scal_cbook is scalar_lloyd's
   dictionary with one more key, 'lagrange_mult', and a test call assigns with
   that value and the dictionary's 'lengths'.  Returns as Mod2_compute_RD_point
-  does, source_code='huffman' and its table slots included."""
+  does, source_code='huffman', its table slots and from_stream included."""
   training = precomputed_scal_codebook is None
   if training:
     scal_codes = _gathered(codes, scal_clusts)
@@ -508,8 +562,8 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                                          precomputed_vec_codebook,
                                          precomputed_vec_codebook_lengths)
   rate, distortion, huff_tab1, huff_tab2 = _mixed_point(
-      'Mod3_compute_RD_point', training, source_code, precomputed_huff_tab1,
-      precomputed_huff_tab2,
+      'Mod3_compute_RD_point', training, source_code, from_stream,
+      precomputed_huff_tab1, precomputed_huff_tab2,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, scal_lengths=scal_cbook['lengths'],
       scal_lagrange_mult=scal_cbook['lagrange_mult'], vec_lengths=vec_cw_len,

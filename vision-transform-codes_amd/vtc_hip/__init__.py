@@ -2,7 +2,7 @@
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
 include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h,
-include/vtc_vq.h and include/vtc_index_code.h).
+include/vtc_vq.h, include/vtc_index_code.h and include/vtc_index_decode.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -310,6 +310,18 @@ INDEX_CODE_SIGNATURES = {
                                    _i64, _vp, _vp]),
 }
 
+INDEX_DECODE_ABI_VERSION = 1   # VTC_INDEX_DECODE_ABI_VERSION
+INDEX_DECODE_LOOKUP_BITS = 10  # VTC_INDEX_DECODE_LOOKUP_BITS
+
+# The tenth header, include/vtc_index_decode.h (same library): packed index
+# streams back to indices.  Again a table of its own.
+INDEX_DECODE_SIGNATURES = {
+    'vtc_index_decode_abi_version': (_i32, []),
+    'vtc_index_code_unpack_workspace_bytes': (_sz, [_i32, _i32]),
+    'vtc_index_code_unpack': (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp,
+                                     _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -328,7 +340,8 @@ def load_library():
   lib = ctypes.CDLL(str(LIBRARY_PATH), mode=os.RTLD_NOW)
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
-                QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES):
+                QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
+                INDEX_DECODE_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -351,6 +364,8 @@ def load_library():
     raise ImportError('libvtc_hip.so vector quantiser ABI version mismatch')
   if lib.vtc_index_code_abi_version() != INDEX_CODE_ABI_VERSION:
     raise ImportError('libvtc_hip.so index code ABI version mismatch')
+  if lib.vtc_index_decode_abi_version() != INDEX_DECODE_ABI_VERSION:
+    raise ImportError('libvtc_hip.so index decode ABI version mismatch')
   _lib = lib
   return lib
 
