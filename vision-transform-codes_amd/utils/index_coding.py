@@ -19,11 +19,22 @@ charges the test codes what those tables cost.  Here
                          inverse of pack_index_streams
   parse_index_stream     one string of '0' / '1', tables -> its m indices
 
+A prefix code spends at least one bit per index; the range coder (rANS) of
+include/vtc_index_ans.h does not:
+
+  index_ans_frequencies  counts -> uint16 (m, kmax) frequencies, each column
+                         summing to 2^15, on the host, pure integers
+  index_ans_stream_bytes indices (b, m), freq -> bytes of every stream
+  pack_index_ans         indices (b, m), freq -> (packed, offsets,
+                         rows_per_stream), offsets in BYTES, one per stream
+  unpack_index_ans       (packed, offsets), freq, b, rows_per_stream -> indices
+
 The per-entry work runs in the kernels of csrc/index_code.hip behind
-include/vtc_index_code.h and, for the way back, of
-csrc/index_decode.hip behind include/vtc_index_decode.h.
-Indices are (b, m) int32 device tensors: m index streams ("columns") per row,
-each with a table of its own, {int index: str of '0' / '1'}.
+include/vtc_index_code.h, for the way back of
+csrc/index_decode.hip behind include/vtc_index_decode.h, and
+of csrc/index_ans.hip.  Indices are (b, m) int32 device tensors: m index
+streams ("columns") per row, each with a table of its own, {int index: str of
+'0' / '1'}, or a row of frequencies.
 """
 import numpy as np
 import torch
@@ -292,3 +303,234 @@ def parse_index_stream(stream, tables):
   indices = unpack_index_streams(torch.from_numpy(host).to(device),
                                  torch.from_numpy(ends).to(device), tables)
   return [int(i) for i in indices[0].tolist()]
+
+
+# ------------------------------------------------------------- range coding
+ANS_PROB_BITS = vtc_hip.INDEX_ANS_PROB_BITS
+ANS_MAX_STREAM_SYMBOLS = 1 << vtc_hip.INDEX_ANS_MAX_STREAM_BITS
+
+
+def index_ans_frequencies(counts, k=None):
+  """uint16 numpy array (m, kmax): the frequencies of the range coder, every
+  column summing to 2^15, from the (m, kmax) counts and the codewords in use k
+  that index_huffman_tables takes.  On the host, Python integers only:
+
+  1. the weight w_i is count_i, or 1 when count_i = 0, for every i < k[j] (so
+     every index the codebook can produce is codable); 0 for i >= k[j];
+  2. f_i = max(1, floor(w_i * 2^15 / W)) for i < k[j], W = sum w_i;
+  3. the difference 2^15 - sum f is given out, or taken back, one unit at a
+     time, going round the symbols in order of (-w_i, i) and skipping symbols
+     at f = 1 when taking."""
+  rows = _host_rows(counts)
+  m, kmax = len(rows), len(rows[0])
+  if kmax > MAX_SYMBOLS:
+    raise NotImplementedError('kmax = %d, at most %d' % (kmax, MAX_SYMBOLS))
+  if k is None:
+    k = [kmax] * m
+  else:
+    if torch.is_tensor(k):
+      k = k.cpu().numpy()
+    k = [int(v) for v in np.asarray(k).reshape(-1)]
+    if len(k) == 1:
+      k = k * m
+  if len(k) != m or min(k) < 1 or max(k) > kmax:
+    raise ValueError('k must hold %d values in [1, %d]' % (m, kmax))
+  scale = 1 << ANS_PROB_BITS
+  freq = np.zeros((m, kmax), dtype=np.uint16)
+  for j, row in enumerate(rows):
+    kj = k[j]
+    if min(row[:kj]) < 0:
+      raise ValueError('column %d has a negative count' % j)
+    w = [c if c > 0 else 1 for c in row[:kj]]
+    total = sum(w)
+    f = [max(1, (wi << ANS_PROB_BITS) // total) for wi in w]
+    order = sorted(range(kj), key=lambda i: (-w[i], i))
+    d = scale - sum(f)
+    # one unit at a time round the order, whole rounds taken at once
+    if d > 0:
+      rounds, rest = divmod(d, kj)
+      for rank, i in enumerate(order):
+        f[i] += rounds + (1 if rank < rest else 0)
+    while d < 0:
+      open_ = [i for i in order if f[i] > 1]   # not empty: sum f > 2^15 >= k
+      rounds = min(-d // len(open_), min(f[i] for i in open_) - 1)
+      if rounds:
+        for i in open_:
+          f[i] -= rounds
+        d += rounds * len(open_)
+      else:                                    # a last, partial round
+        for i in open_[:-d]:
+          f[i] -= 1
+        d = 0
+    freq[j, :kj] = f
+  return freq
+
+
+def _ans_freq(freq, m, device):
+  """The (m, kmax) uint16 frequencies as a device tensor of int16 bit
+  patterns (torch moves bytes), and kmax."""
+  if torch.is_tensor(freq):
+    freq = freq.cpu().numpy()
+  freq = np.asarray(freq)
+  if freq.ndim == 1:
+    freq = freq[None, :]
+  if freq.dtype != np.uint16 or freq.ndim != 2 or freq.shape[1] < 1:
+    raise ValueError('freq must be a uint16 (m, kmax) array')
+  if freq.shape[0] != m:
+    raise ValueError('%d rows of frequencies for %d columns'
+                     % (freq.shape[0], m))
+  if m > MAX_COLUMNS:
+    raise NotImplementedError('m = %d, at most %d' % (m, MAX_COLUMNS))
+  if freq.shape[1] > MAX_SYMBOLS:
+    raise NotImplementedError('kmax = %d, at most %d'
+                              % (freq.shape[1], MAX_SYMBOLS))
+  sums = freq.astype(np.int64).sum(1)
+  wrong = np.nonzero(sums != 1 << ANS_PROB_BITS)[0]
+  if len(wrong):
+    raise ValueError('the frequencies of column %d sum to %d, not 2^%d'
+                     % (wrong[0], sums[wrong[0]], ANS_PROB_BITS))
+  host = np.ascontiguousarray(freq).view(np.int16)
+  return torch.from_numpy(host).to(device), int(freq.shape[1])
+
+
+def _ans_rows(rows_per_stream, m):
+  if rows_per_stream is None:
+    return max(1, 65536 // m)
+  rows = int(rows_per_stream)
+  if rows < 1 or rows * m > ANS_MAX_STREAM_SYMBOLS:
+    raise ValueError('rows_per_stream = %d: at least 1 and at most %d symbols '
+                     'in a stream' % (rows, ANS_MAX_STREAM_SYMBOLS))
+  return rows
+
+
+def _raise_ans_status(indices, status, what):
+  uncodable, first, bad = status.tolist()
+  if bad:   # _ans_freq saw the same frequencies
+    raise ValueError('%s: the frequencies of column %d do not sum to 2^%d'
+                     % (what, bad - 1, ANS_PROB_BITS))
+  if uncodable:
+    row, column = divmod(first - 1, indices.shape[1])
+    raise KeyError('%s: column %d has no frequency for index %d (row %d); %d '
+                   'such entries' % (what, column, int(indices[row, column]),
+                                     row, uncodable))
+
+
+def _ans_sizes(lib, indices, freq, kmax, rows, ws, status):
+  b, m = indices.shape
+  device = indices.device
+  sizes = torch.empty(-(-b // rows), dtype=torch.int32, device=device)
+  vtc_hip.check(lib.vtc_index_ans_sizes(
+      vtc_hip.ptr(indices), b, m, vtc_hip.ptr(freq), kmax, rows,
+      vtc_hip.ptr(sizes), vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), 'vtc_index_ans_sizes')
+  return sizes
+
+
+def index_ans_stream_bytes(indices, freq, rows_per_stream=None):
+  """int32 device tensor [ceil(b / rows_per_stream)]: the bytes of every
+  stream of the (b, m) indices under the (m, kmax) frequencies, 256 of end
+  states and two per word.  rows_per_stream defaults to max(1, 65536 // m),
+  which puts the 256-byte flush at about 0.03 bit per index.  One host read
+  (the status).  An index of frequency 0 (the -1 of a NaN code among them)
+  raises KeyError naming the column and the index."""
+  lib = vtc_hip.load_library()
+  indices = _indices(indices)
+  m, device = indices.shape[1], indices.device
+  rows = _ans_rows(rows_per_stream, m)
+  freq, kmax = _ans_freq(freq, m, device)
+  ws = vtc_hip.workspace(lib.vtc_index_ans_workspace_bytes(m, kmax), device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  sizes = _ans_sizes(lib, indices, freq, kmax, rows, ws, status)
+  _raise_ans_status(indices, status, 'index_ans_stream_bytes')
+  return sizes
+
+
+def pack_index_ans(indices, freq, rows_per_stream=None):
+  """(packed, offsets, rows_per_stream): the range-coded streams of the (b, m)
+  indices back to back in one uint8 device tensor, the (n + 1,) int64 device
+  tensor of the BYTE at which each of the n = ceil(b / rows_per_stream)
+  streams starts, the total last, and the rows of a stream (the default of
+  index_ans_stream_bytes when None), which the decoder needs again.  Stream s
+  holds rows s * rows_per_stream and on in row-major order
+  (include/vtc_index_ans.h)."""
+  from utils import jpeg
+  lib = vtc_hip.load_library()
+  indices = _indices(indices)
+  b, m = indices.shape
+  device = indices.device
+  rows = _ans_rows(rows_per_stream, m)
+  freq, kmax = _ans_freq(freq, m, device)
+  ws = vtc_hip.workspace(lib.vtc_index_ans_workspace_bytes(m, kmax), device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  sizes = _ans_sizes(lib, indices, freq, kmax, rows, ws, status)
+  _raise_ans_status(indices, status, 'pack_index_ans')
+  offsets = jpeg.bit_offsets(sizes)   # a plain prefix sum: bytes here
+  total = int(offsets[-1])
+  packed = torch.empty(total, dtype=torch.uint8, device=device)
+  vtc_hip.check(lib.vtc_index_ans_pack(
+      vtc_hip.ptr(indices), b, m, vtc_hip.ptr(freq), kmax, rows,
+      vtc_hip.ptr(sizes), vtc_hip.ptr(offsets), vtc_hip.ptr(packed), total,
+      vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), 'vtc_index_ans_pack')
+  skipped = int(status[2])
+  if skipped:
+    raise ValueError('pack_index_ans: %d streams outside the output'
+                     % skipped)
+  return packed, offsets, rows
+
+
+def unpack_index_ans(packed, offsets, freq, b, rows_per_stream, exact=True):
+  """indices (b, m) int32 device tensor from what pack_index_ans returns;
+  m = len(freq).  Stream s reads from byte offsets[s] on and may use the bytes
+  below offsets[s + 1].
+
+  ValueError for frequencies that do not sum to 2^15 (before any device
+  work), for malformed streams (their number and the first one named;
+  include/vtc_index_ans.h lists what makes a stream malformed: bad offsets, a
+  slot without its 256 bytes of states, a stream that runs out of words, end
+  states that are not 2^16) and, with exact=True, for streams that leave bytes
+  of their span unread.  VtcHipError for a CPU tensor.  One host read."""
+  packed = vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
+  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
+  b = int(b)
+  host_freq = freq.cpu().numpy() if torch.is_tensor(freq) else np.asarray(freq)
+  m = 1 if host_freq.ndim == 1 else host_freq.shape[0]
+  if b < 1:
+    raise ValueError('b must be at least 1')
+  rows = _ans_rows(rows_per_stream, m)
+  n = -(-b // rows)
+  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] != n + 1:
+    raise ValueError('packed must be (bytes,) and offsets (%d,) for %d rows in '
+                     'streams of %d, got shapes %s and %s'
+                     % (n + 1, b, rows, tuple(packed.shape),
+                        tuple(offsets.shape)))
+  lib = vtc_hip.load_library()
+  packed, offsets = packed.contiguous(), offsets.contiguous()
+  device = packed.device
+  freq, kmax = _ans_freq(host_freq, m, device)
+  indices = torch.empty((b, m), dtype=torch.int32, device=device)
+  used = torch.empty(n, dtype=torch.int32, device=device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  ws = vtc_hip.workspace(lib.vtc_index_ans_workspace_bytes(m, kmax), device)
+  bytes_from = packed if packed.numel() else ws   # never read when empty
+  vtc_hip.check(lib.vtc_index_ans_unpack(
+      vtc_hip.ptr(bytes_from), packed.numel(), vtc_hip.ptr(offsets), b, m,
+      vtc_hip.ptr(freq), kmax, rows, vtc_hip.ptr(indices), vtc_hip.ptr(used),
+      vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), 'vtc_index_ans_unpack')
+  loose = used.to(torch.int64) != offsets[1:] - offsets[:-1]
+  report = torch.cat([status, torch.stack([
+      loose.sum(), loose.to(torch.int32).argmax().to(torch.int64)])])
+  malformed, first, bad, loose, first_loose = report.tolist()
+  if bad:   # _ans_freq saw the same frequencies
+    raise ValueError('unpack_index_ans: the frequencies of column %d do not '
+                     'sum to 2^%d' % (bad - 1, ANS_PROB_BITS))
+  if malformed:
+    raise ValueError('unpack_index_ans: %d malformed streams of %d, the first '
+                     'is stream %d (rows %d and on)'
+                     % (malformed, n, first - 1, (first - 1) * rows))
+  if exact and loose:
+    raise ValueError('unpack_index_ans: %d streams of %d do not use up their '
+                     'span of bytes, the first is stream %d'
+                     % (loose, n, first_loose))
+  return indices

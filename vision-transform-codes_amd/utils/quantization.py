@@ -363,7 +363,8 @@ def _distortion(patches, reconstruction, fullimg_reshape_params):
 
 def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
                      lagrange_mult=0.0, source_code='jpeg', tables=None,
-                     fullimg_reshape_params=None, from_stream=False):
+                     fullimg_reshape_params=None, from_stream=False,
+                     rows_per_stream=None):
   """One rate-distortion point of quantised codes.
 
   codes : (b, s) float32 device tensor; patches : (b, n) float32 device
@@ -383,12 +384,20 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   codable, seen or not), and the rate is the total of index_code_bits, the
   bits a decoder would read.  With tables trained on other data this is an
   out-of-sample rate, which no entropy figure of the data itself gives.
+  'ans': every column's indices under a row of range-coder frequencies
+  (index_coding.index_ans_frequencies, include/vtc_index_ans.h); `tables` is
+  the uint16 (s, kmax) frequency array, trained on these indices when None,
+  and the rate is 8 x the total bytes of the streams of
+  index_coding.index_ans_stream_bytes with `rows_per_stream` rows each (None:
+  its default), the 256-byte flush of every stream included.  A prefix code
+  pays at least one bit per index; this one does not.
 
-  from_stream (source_code 'huffman' only, ValueError otherwise): the indices
-  are packed with index_coding.pack_index_streams and read back by
-  decode_codes; reconstruction and distortion are those of the decoded codes
-  and the rate is the streams' total bits / patches.numel().  What is charged
-  has then been decoded, and what is measured has been through the bytes.
+  from_stream (source_code 'huffman' and 'ans' only, ValueError otherwise):
+  the indices are packed with index_coding.pack_index_streams
+  (pack_index_ans) and read back by decode_codes; reconstruction and
+  distortion are those of the decoded codes and the rate is the streams' total
+  bits / patches.numel().  What is charged has then been decoded, and what is
+  measured has been through the bytes.
 
   Returns (rate in bits per pixel, distortion, tables).  distortion is
   {'pSNR': utils.plotting.compute_pSNR(patches, reconstruction)}; with
@@ -397,8 +406,9 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   'SSIM'} of the images, with the patch figure under 'pSNR_patches'.
   """
   from utils import jpeg
-  if source_code not in ('jpeg', 'entropy', 'huffman'):
-    raise ValueError("source_code must be 'jpeg', 'entropy' or 'huffman'")
+  if source_code not in ('jpeg', 'entropy', 'huffman', 'ans'):
+    raise ValueError("source_code must be 'jpeg', 'entropy', 'huffman' or "
+                     "'ans'")
   _check_from_stream(from_stream, source_code)
   codes = _codes(codes)
   patches = _codes(patches, 'patches')
@@ -437,6 +447,19 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
                                     dictionary)
     else:
       total_bits, tables = _huffman_bits(indices, tables, counts_and_k)
+  elif source_code == 'ans':
+    if int(status) != 0:   # before the coder meets their index -1
+      raise ValueError('compute_RD_point: the codes hold NaN')
+    counts_and_k = lambda: (index_counts(indices, pair[0].shape[1]), pair[1])
+    if from_stream:
+      total_bits, tables, streams = _ans_streams(indices, tables, counts_and_k,
+                                                 rows_per_stream)
+      reconstruction = _reconstruct(
+          decode_codes(streams[0], streams[1], tables, pair,
+                       ans_shape=(indices.shape[0], streams[2])), dictionary)
+    else:
+      total_bits, tables = _ans_bits(indices, tables, counts_and_k,
+                                     rows_per_stream)
   else:
     total_bits = entropy_bits(index_counts(indices, pair[0].shape[1]))
   if int(status) != 0:
@@ -466,30 +489,71 @@ def _huffman_streams(indices, tables, counts_and_k):
   return int(offsets[-1]), tables, (packed, offsets)
 
 
+def _ans_bits(indices, tables, counts_and_k, rows_per_stream):
+  """(8 x the bytes of the range-coded streams of the (b, m) indices, the
+  frequencies): a uint16 (m, kmax) array, trained on counts_and_k() when
+  None."""
+  from utils import index_coding
+  if tables is None:
+    tables = index_coding.index_ans_frequencies(*counts_and_k())
+  sizes = index_coding.index_ans_stream_bytes(indices, tables, rows_per_stream)
+  return 8 * int(sizes.sum()), tables
+
+
+def _ans_streams(indices, tables, counts_and_k, rows_per_stream):
+  """_ans_bits from the packed streams: (their total bits, the frequencies,
+  (packed, offsets, rows_per_stream))."""
+  from utils import index_coding
+  if tables is None:
+    tables = index_coding.index_ans_frequencies(*counts_and_k())
+  streams = index_coding.pack_index_ans(indices, tables, rows_per_stream)
+  return 8 * int(streams[1][-1]), tables, streams
+
+
+# the source codes that have tables and write streams of indices
+_TABLE_CODES = ('huffman', 'ans')
+
+
 def _check_from_stream(from_stream, source_code):
-  if from_stream and source_code != 'huffman':
-    raise ValueError("from_stream=True needs source_code='huffman': only "
-                     'that source code writes streams of indices')
+  if from_stream and source_code not in _TABLE_CODES:
+    raise ValueError("from_stream=True needs source_code='huffman' or 'ans': "
+                     'only those source codes write streams of indices')
 
 
-def decode_codes(packed, offsets, tables, codebooks):
+def _unpack_indices(packed, offsets, tables, ans_shape):
+  from utils import index_coding
+  if ans_shape is None:
+    return index_coding.unpack_index_streams(packed, offsets, tables)
+  b, rows_per_stream = ans_shape
+  return index_coding.unpack_index_ans(packed, offsets, tables, b,
+                                       rows_per_stream)
+
+
+def decode_codes(packed, offsets, tables, codebooks, ans_shape=None):
   """The (b, s) float32 dequantised codes whose index streams are in (packed,
   offsets), what index_coding.pack_index_streams returns for the (b, s)
   indices of `assign`: index_coding.unpack_index_streams under the s tables,
   then dequantize_assignments with the codebooks.  One host read (the
-  decoder's status)."""
-  from utils import index_coding
+  decoder's status).
+
+  ans_shape = (b, rows_per_stream): (packed, offsets) are the range-coded
+  streams of index_coding.pack_index_ans instead, `tables` the uint16 (s,
+  kmax) frequencies, and index_coding.unpack_index_ans reads them."""
   return dequantize_assignments(
-      index_coding.unpack_index_streams(packed, offsets, tables), codebooks)
+      _unpack_indices(packed, offsets, tables, ans_shape), codebooks)
 
 
 def _check_source_code(source_code):
-  if source_code not in ('entropy', 'huffman'):
-    raise ValueError("source_code must be 'entropy' or 'huffman'")
+  if source_code not in ('entropy',) + _TABLE_CODES:
+    raise ValueError("source_code must be 'entropy', 'huffman' or 'ans'")
 
 
-def _need_tables(who, *tables):
+def _need_tables(who, *tables, source_code='huffman'):
   if any(table is None for table in tables):
+    if source_code == 'ans':
+      raise ValueError("%s: source_code='ans' with precomputed codebooks "
+                       'needs the frequencies of the training call as well'
+                       % who)
     raise ValueError("%s: source_code='huffman' with precomputed codebooks "
                      'needs the Huffman tables of the training call as well'
                      % who)
@@ -535,7 +599,8 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
                               precomputed_huff_tab1=None,
                               precomputed_huff_tab2=None,
                               fullimg_reshape_params=None,
-                              source_code='entropy', from_stream=False):
+                              source_code='entropy', from_stream=False,
+                              rows_per_stream=None):
   """The experiment's baseline_compute_RD_point: uniform codebooks with bins
   of binwidths * quant_multiplier.  The return slots are those of the
   experiment, (rate, distortion, codebook, huff_tab1, huff_tab2) from the
@@ -553,22 +618,28 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   scalar tables and huff_tab2 = None, and a test call (precomputed_codebook
   and precomputed_huff_tab1) measures the bits of the test indices under the
   trained tables.  Precomputed codebooks without the tables raise
-  ValueError.  from_stream: as in compute_RD_point."""
+  ValueError.  from_stream: as in compute_RD_point.
+
+  source_code 'ans': as 'huffman' with the range coder of compute_RD_point;
+  huff_tab1 is then the uint16 (s, kmax) frequency array, and rows_per_stream
+  is that of compute_RD_point."""
   _check_source_code(source_code)
   _check_from_stream(from_stream, source_code)
   training = precomputed_codebook is None
-  if source_code == 'huffman' and not training:
-    _need_tables('baseline_compute_RD_point', precomputed_huff_tab1)
+  if source_code in _TABLE_CODES and not training:
+    _need_tables('baseline_compute_RD_point', precomputed_huff_tab1,
+                 source_code=source_code)
   codebook = (_uniform_for(codes, binwidths, quant_multiplier) if training
               else precomputed_codebook)
   rate, distortion, tables = compute_RD_point(
       codes, patches, dictionary, codebook, source_code=source_code,
-      tables=(precomputed_huff_tab1 if source_code == 'huffman' and
+      tables=(precomputed_huff_tab1 if source_code in _TABLE_CODES and
               not training else None),
-      fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream)
+      fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream,
+      rows_per_stream=rows_per_stream)
   if training:
     return (rate, distortion, codebook,
-            tables if source_code == 'huffman' else None, None)
+            tables if source_code in _TABLE_CODES else None, None)
   return rate, distortion
 
 
@@ -578,7 +649,7 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
                           precomputed_huff_tab1=None,
                           fullimg_reshape_params=None, max_iterations=50,
                           epsilon=1e-5, source_code='entropy',
-                          from_stream=False):
+                          from_stream=False, rows_per_stream=None):
   """The experiment's Mod1_compute_RD_point: entropy-constrained scalar Lloyd
   quantisers (scalar_lloyd) started from uniform codebooks of bin width
   init_binwidths, with lagrange_mult = quant_multiplier; the rate is the
@@ -592,12 +663,14 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   With source_code='huffman' the rate is the bits of the indices under one
   Huffman table per column, huff_tab1 is the list of those s tables, and a
   test call takes them back as precomputed_huff_tab1 (ValueError without
-  them), as baseline_compute_RD_point does; from_stream likewise."""
+  them), as baseline_compute_RD_point does; from_stream likewise, and
+  source_code='ans' with rows_per_stream (huff_tab1 the frequency array)."""
   _check_source_code(source_code)
   _check_from_stream(from_stream, source_code)
   training = precomputed_codebook is None
-  if source_code == 'huffman' and not training:
-    _need_tables('Mod1_compute_RD_point', precomputed_huff_tab1)
+  if source_code in _TABLE_CODES and not training:
+    _need_tables('Mod1_compute_RD_point', precomputed_huff_tab1,
+                 source_code=source_code)
   if training:
     fit = scalar_lloyd(codes, _uniform_for(codes, init_binwidths, 1.0),
                        lagrange_mult=quant_multiplier,
@@ -608,10 +681,11 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   rate, distortion, tables = compute_RD_point(
       codes, patches, dictionary, codebook, lengths=lengths,
       lagrange_mult=quant_multiplier, source_code=source_code,
-      tables=(precomputed_huff_tab1 if source_code == 'huffman' and
+      tables=(precomputed_huff_tab1 if source_code in _TABLE_CODES and
               not training else None),
-      fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream)
+      fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream,
+      rows_per_stream=rows_per_stream)
   if training:
     return (rate, distortion, codebook, lengths,
-            tables if source_code == 'huffman' else None)
+            tables if source_code in _TABLE_CODES else None)
   return rate, distortion

@@ -295,7 +295,8 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                            scal_lengths=None, scal_lagrange_mult=0.0,
                            vec_lengths=None, vec_lagrange_mult=0.0,
                            fullimg_reshape_params=None, source_code='entropy',
-                           tables=None, from_stream=False):
+                           tables=None, from_stream=False,
+                           rows_per_stream=None):
   """One rate-distortion point of codes quantised in two parts.
 
   codes : (b, s) float32 device tensor; patches : (b, n); dictionary : (s, n),
@@ -322,10 +323,18 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   index_code_bits / patches.numel(), and a third value is returned: the
   tables.
 
-  from_stream (source_code 'huffman' only, ValueError otherwise): that index
-  array is packed with index_coding.pack_index_streams and read back by
-  decode_codes_mixed; reconstruction and distortion are those of the decoded
-  codes and the rate is the streams' total bits / patches.numel()."""
+  source_code 'ans': the same index array under the range coder of
+  quantization.compute_RD_point.  `tables` = (scalar frequencies uint16
+  (len(scal_clusts), kmax), vector frequencies uint16 (kmax',)), trained on
+  these indices when None and padded with zeros to the larger kmax for the
+  device; the rate is 8 x the bytes of the streams of rows_per_stream rows /
+  patches.numel(), and the third value is that pair.
+
+  from_stream (source_code 'huffman' and 'ans' only, ValueError otherwise):
+  that index array is packed with index_coding.pack_index_streams
+  (pack_index_ans) and read back by decode_codes_mixed; reconstruction and
+  distortion are those of the decoded codes and the rate is the streams' total
+  bits / patches.numel()."""
   _scalar._check_source_code(source_code)
   _scalar._check_from_stream(from_stream, source_code)
   codes = _scalar._codes(codes)
@@ -382,6 +391,28 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                              (vec_values, vec_k), s), dictionary)
     else:
       total_bits, _ = _scalar._huffman_bits(streams, all_tables, None)
+  elif source_code == 'ans':
+    from utils import index_coding
+    if tables is None:
+      tables = (
+          index_coding.index_ans_frequencies(
+              index_counts(scal_indices, scal_pair[0].shape[1]), scal_pair[1]),
+          index_coding.index_ans_frequencies(
+              vector_index_counts(vec_indices, vec_values.shape[0]),
+              vec_k)[0])
+    scalar_tables, vector_table = tables
+    streams = torch.cat([scal_indices, vec_indices[:, None]], 1)
+    all_tables = _stacked_frequencies(scalar_tables, vector_table)
+    if from_stream:
+      total_bits, _, (packed, offsets, rows) = _scalar._ans_streams(
+          streams, all_tables, None, rows_per_stream)
+      reconstruction = _scalar._reconstruct(
+          decode_codes_mixed(packed, offsets, all_tables, scal, scal_pair, vec,
+                             (vec_values, vec_k), s, ans_shape=(b, rows)),
+          dictionary)
+    else:
+      total_bits, _ = _scalar._ans_bits(streams, all_tables, None,
+                                        rows_per_stream)
   else:
     total_bits = (
         entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
@@ -392,11 +423,28 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                                    fullimg_reshape_params)
   if source_code == 'huffman':
     return rate, distortion, (list(scalar_tables), vector_table)
+  if source_code == 'ans':
+    return rate, distortion, (scalar_tables, vector_table)
   return rate, distortion
 
 
+def _stacked_frequencies(scalar_freq, vector_freq):
+  """The uint16 (len(scal_clusts) + 1, kmax) frequencies of the combined index
+  array: the scalar rows, then the vector row, padded with zeros (absent
+  symbols) to the larger kmax."""
+  scalar_freq = np.asarray(scalar_freq)
+  vector_freq = np.asarray(vector_freq).reshape(1, -1)
+  if scalar_freq.ndim != 2:
+    raise ValueError('the scalar frequencies must be (len(scal_clusts), kmax)')
+  kmax = max(scalar_freq.shape[1], vector_freq.shape[1])
+  out = np.zeros((scalar_freq.shape[0] + 1, kmax), dtype=np.uint16)
+  out[:-1, :scalar_freq.shape[1]] = scalar_freq
+  out[-1, :vector_freq.shape[1]] = vector_freq[0]
+  return out
+
+
 def decode_codes_mixed(packed, offsets, tables, scal_clusts, scal_codebooks,
-                       vec_clust, vec_codebook, s):
+                       vec_clust, vec_codebook, s, ans_shape=None):
   """The (b, s) float32 dequantised codes whose index streams are in (packed,
   offsets), the layout compute_RD_point_mixed codes: one row per patch, the
   scalar indices first in scal_clusts order, the vector index last.  `tables`
@@ -404,18 +452,22 @@ def decode_codes_mixed(packed, offsets, tables, scal_clusts, scal_codebooks,
   index_coding.unpack_index_streams, then quantization.dequantize_assignments
   into the columns scal_clusts and vector_dequantize into the columns
   vec_clust; a column in neither cluster is zero.  One host read (the
-  decoder's status)."""
-  from utils import index_coding
+  decoder's status).
+
+  ans_shape = (b, rows_per_stream): the streams are those of
+  index_coding.pack_index_ans, `tables` the uint16 (len(scal_clusts) + 1,
+  kmax) frequencies in that order, read by index_coding.unpack_index_ans."""
   s = int(s)
   scal = _cluster(scal_clusts, s, 'scal_clusts')
   vec = _cluster(vec_clust, s, 'vec_clust')
   if len(set(scal + vec)) != len(scal) + len(vec):
     raise ValueError('scal_clusts and vec_clust overlap')
-  tables = list(tables)
+  if ans_shape is None:
+    tables = list(tables)
   if len(tables) != len(scal) + 1:
     raise ValueError('%d tables for %d scalar columns and the vector column'
                      % (len(tables), len(scal)))
-  indices = index_coding.unpack_index_streams(packed, offsets, tables)
+  indices = _scalar._unpack_indices(packed, offsets, tables, ans_shape)
   device = indices.device
   scal_deq = _scalar.dequantize_assignments(
       indices[:, :len(scal)].contiguous(), scal_codebooks)
@@ -447,21 +499,21 @@ def _fit_vector_part(codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
                       max_iterations=max_iterations, epsilon=epsilon)
 
 
-def _mixed_point(who, training, source_code, from_stream, huff_tab1,
-                 huff_tab2, *args, **kwargs):
+def _mixed_point(who, training, source_code, from_stream, rows_per_stream,
+                 huff_tab1, huff_tab2, *args, **kwargs):
   """compute_RD_point_mixed for Mod2 / Mod3: (rate, distortion, huff_tab1,
   huff_tab2), the two tables None under 'entropy'."""
   _scalar._check_source_code(source_code)
   _scalar._check_from_stream(from_stream, source_code)
-  if source_code != 'huffman':
+  if source_code not in _scalar._TABLE_CODES:
     return compute_RD_point_mixed(*args, **kwargs) + (None, None)
   tables = None
   if not training:
-    _scalar._need_tables(who, huff_tab1, huff_tab2)
+    _scalar._need_tables(who, huff_tab1, huff_tab2, source_code=source_code)
     tables = (huff_tab1, huff_tab2)
   rate, distortion, tables = compute_RD_point_mixed(
-      *args, source_code='huffman', tables=tables, from_stream=from_stream,
-      **kwargs)
+      *args, source_code=source_code, tables=tables, from_stream=from_stream,
+      rows_per_stream=rows_per_stream, **kwargs)
   return rate, distortion, tables[0], tables[1]
 
 
@@ -476,7 +528,7 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
                           epsilon=1e-5, source_code='entropy',
-                          from_stream=False):
+                          from_stream=False, rows_per_stream=None):
   """The experiment's Mod2_compute_RD_point, with (b, s) codes (module
   docstring): the columns scal_clusts get uniform scalar codebooks of bin
   width scal_binwidths * scal_quant_multiplier (as in
@@ -501,7 +553,9 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   the vector table, huff_tab3 = None, and a test call takes the first two back
   as precomputed_huff_tab1 and precomputed_huff_tab2 and measures the bits of
   the test indices under them.  Precomputed codebooks without both tables
-  raise ValueError.  from_stream is that of compute_RD_point_mixed."""
+  raise ValueError.  from_stream is that of compute_RD_point_mixed, and so
+  are source_code='ans' and rows_per_stream: huff_tab1 and huff_tab2 are then
+  the scalar and the vector frequency arrays."""
   training = precomputed_scal_codebook is None
   if training:
     scal_cbook = _scalar._uniform_for(_gathered(codes, scal_clusts),
@@ -515,6 +569,7 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                                          precomputed_vec_codebook_lengths)
   rate, distortion, huff_tab1, huff_tab2 = _mixed_point(
       'Mod2_compute_RD_point', training, source_code, from_stream,
+      rows_per_stream,
       precomputed_huff_tab1, precomputed_huff_tab2,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, vec_lengths=vec_cw_len,
@@ -537,7 +592,7 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
                           epsilon=1e-5, source_code='entropy',
-                          from_stream=False):
+                          from_stream=False, rows_per_stream=None):
   """The experiment's Mod3_compute_RD_point: Mod2_compute_RD_point with
   entropy-constrained scalar quantisers, scalar_lloyd from uniform codebooks
   of bin width scal_binwidths with lagrange_mult = scal_quant_multiplier (as
@@ -545,7 +600,8 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   scalar multiplier again, so the returned scal_cbook is scalar_lloyd's
   dictionary with one more key, 'lagrange_mult', and a test call assigns with
   that value and the dictionary's 'lengths'.  Returns as Mod2_compute_RD_point
-  does, source_code='huffman', its table slots and from_stream included."""
+  does, source_code='huffman' and 'ans', their table slots, from_stream and
+  rows_per_stream included."""
   training = precomputed_scal_codebook is None
   if training:
     scal_codes = _gathered(codes, scal_clusts)
@@ -563,6 +619,7 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                                          precomputed_vec_codebook_lengths)
   rate, distortion, huff_tab1, huff_tab2 = _mixed_point(
       'Mod3_compute_RD_point', training, source_code, from_stream,
+      rows_per_stream,
       precomputed_huff_tab1, precomputed_huff_tab2,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, scal_lengths=scal_cbook['lengths'],

@@ -2,7 +2,8 @@
 Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
 include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h,
-include/vtc_vq.h, include/vtc_index_code.h and include/vtc_index_decode.h).
+include/vtc_vq.h, include/vtc_index_code.h, include/vtc_index_decode.h and
+include/vtc_index_ans.h).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -322,6 +323,25 @@ INDEX_DECODE_SIGNATURES = {
                                      _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+INDEX_ANS_ABI_VERSION = 1   # VTC_INDEX_ANS_ABI_VERSION of vtc_index_ans.h
+INDEX_ANS_PROB_BITS = 15    # VTC_INDEX_ANS_PROB_BITS
+INDEX_ANS_LANES = 64        # VTC_INDEX_ANS_LANES
+INDEX_ANS_MAX_STREAM_BITS = 24   # VTC_INDEX_ANS_MAX_STREAM_BITS
+
+# The eleventh header, include/vtc_index_ans.h (same library): range coding of
+# quantiser indices, sizes, packed streams and the decoder.  Again a table of
+# its own.
+INDEX_ANS_SIGNATURES = {
+    'vtc_index_ans_abi_version': (_i32, []),
+    'vtc_index_ans_workspace_bytes': (_sz, [_i32, _i32]),
+    'vtc_index_ans_sizes': (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp,
+                                   _vp, _sz, _vp]),
+    'vtc_index_ans_pack': (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp,
+                                  _vp, _i64, _vp, _vp, _sz, _vp]),
+    'vtc_index_ans_unpack': (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i32,
+                                    _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -341,7 +361,7 @@ def load_library():
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
                 QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
-                INDEX_DECODE_SIGNATURES):
+                INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -366,6 +386,8 @@ def load_library():
     raise ImportError('libvtc_hip.so index code ABI version mismatch')
   if lib.vtc_index_decode_abi_version() != INDEX_DECODE_ABI_VERSION:
     raise ImportError('libvtc_hip.so index decode ABI version mismatch')
+  if lib.vtc_index_ans_abi_version() != INDEX_ANS_ABI_VERSION:
+    raise ImportError('libvtc_hip.so index ANS ABI version mismatch')
   _lib = lib
   return lib
 
