@@ -11,6 +11,17 @@ superset of utils.quantization, so the experiment needs one changed line:
 The hot paths are the kernels of csrc/vq.hip behind include/vtc_vq.h
 (DESIGN.md 4.16); device tensors in, device tensors out.
 
+Codebooks of more than 4096 codewords.  include/vtc_vq.h stops at
+VQ_MAX_CODEWORDS = 4096 and every default here stops there with it.  The
+keyword max_codewords (vec_max_codewords in the R-D points), at most
+VQ_LARGE_MAX_CODEWORDS = 131072, raises the limit: a codebook of kmax <= 4096
+slots goes through the same entry points as ever, one of 4096 < kmax <=
+max_codewords through their twins of include/vtc_vq_large.h (csrc/vq_large.hip,
+DESIGN.md 4.20), which return the same bits where both apply, and a larger one
+raises NotImplementedError naming the limit in force.  Index coding stops at
+4096 symbols: source_code 'huffman' and 'ans' need a vector codebook of at most
+4096 slots, which trim_vector_codebook makes of a fit that ended there.
+
 A vector quantiser of (b, d) vectors is described by
   codebook   float64 (kmax, d)  the codewords; the slots past k are never read
   k          int32   [1]        codewords in use
@@ -45,21 +56,38 @@ from utils.quantization import (   # noqa: F401  the names the experiment uses
 
 VQ_MAX_DIM = vtc_hip.VQ_MAX_DIM
 VQ_MAX_CODEWORDS = vtc_hip.VQ_MAX_CODEWORDS
+VQ_LARGE_MAX_CODEWORDS = vtc_hip.VQ_LARGE_MAX_CODEWORDS
+
+
+def _limit(max_codewords):
+  max_codewords = int(max_codewords)
+  if not 1 <= max_codewords <= VQ_LARGE_MAX_CODEWORDS:
+    raise ValueError('max_codewords = %d, from 1 to %d'
+                     % (max_codewords, VQ_LARGE_MAX_CODEWORDS))
+  return max_codewords
+
+
+def _entry(lib, name, kmax):
+  """The entry point `name` for a codebook of kmax slots: include/vtc_vq.h up
+  to 4096 of them, include/vtc_vq_large.h above."""
+  prefix = 'vtc_vq_' if kmax <= VQ_MAX_CODEWORDS else 'vtc_vq_large_'
+  return getattr(lib, prefix + name), prefix + name
 
 
 # ------------------------------------------------------------------ host side
-def _initial_codebook_host(vectors, num_bins):
+def _initial_codebook_host(vectors, num_bins, max_codewords=VQ_MAX_CODEWORDS):
   """initial_vector_codebook on a (b, d) numpy array: float64 (k, d)."""
   vectors = np.asarray(vectors, dtype=np.float32)
   b, d = vectors.shape
-  m = max(1, min(int(num_bins), b, VQ_MAX_CODEWORDS))
+  max_codewords = _limit(max_codewords)
+  m = max(1, min(int(num_bins), b, max_codewords))
   picked = vectors[(np.arange(m, dtype=np.int64) * b) // m]
   picked = picked[~np.isnan(picked).any(1)]
   rows = np.concatenate([np.zeros((1, d), np.float32), picked])
   rows = np.where(rows == 0, np.float32(0.0), rows)          # -0.0 is 0.0
   keys = np.ascontiguousarray(rows).view(np.uint32).reshape(len(rows), d)
   _, first = np.unique(keys, axis=0, return_index=True)
-  return rows[np.sort(first)][:VQ_MAX_CODEWORDS].astype(np.float64)
+  return rows[np.sort(first)][:max_codewords].astype(np.float64)
 
 
 def _vectors(vectors, name='vectors'):
@@ -73,8 +101,9 @@ def _vectors(vectors, name='vectors'):
   return vectors.contiguous()
 
 
-def _device_codebook(codebook, d, device):
+def _device_codebook(codebook, d, device, max_codewords=VQ_MAX_CODEWORDS):
   """(codebook float64 (kmax, d), k int32 [1], lengths or None) on `device`."""
+  max_codewords = _limit(max_codewords)
   lengths, k = None, None
   if isinstance(codebook, dict):
     lengths = codebook.get('lengths')
@@ -87,9 +116,9 @@ def _device_codebook(codebook, d, device):
   kmax = int(codebook.shape[0])
   if kmax < 1:
     raise ValueError('codebook must hold at least one codeword')
-  if kmax > VQ_MAX_CODEWORDS:
+  if kmax > max(max_codewords, VQ_MAX_CODEWORDS):
     raise NotImplementedError('kmax = %d, at most %d'
-                              % (kmax, VQ_MAX_CODEWORDS))
+                              % (kmax, max(max_codewords, VQ_MAX_CODEWORDS)))
   if k is None:
     k = np.array([kmax], np.int32)
   elif not torch.is_tensor(k):
@@ -99,49 +128,53 @@ def _device_codebook(codebook, d, device):
 
 
 # ---------------------------------------------------------------- device side
-def initial_vector_codebook(vectors, num_bins):
+def initial_vector_codebook(vectors, num_bins, max_codewords=VQ_MAX_CODEWORDS):
   """A deterministic starting codebook for vector_lloyd: float64 (k, d) device
   tensor whose row 0 is the zero vector.
 
   The candidates are the rows floor(i * b / m), i = 0 .. m - 1, of the (b, d)
-  float32 device tensor `vectors`, with m = min(num_bins, b, 4096); rows with
-  a NaN are skipped, the zero vector is put in front, bitwise duplicates are
-  removed (first occurrences stay, -0.0 counts as 0.0) and at most 4096 rows
-  are kept.  Plumbing: a gather on the device, the comparison of at most 4097
-  rows on the host.
+  float32 device tensor `vectors`, with m = min(num_bins, b, max_codewords);
+  rows with a NaN are skipped, the zero vector is put in front, bitwise
+  duplicates are removed (first occurrences stay, -0.0 counts as 0.0) and at
+  most max_codewords rows are kept.  Plumbing: a gather on the device, one
+  transfer, the comparison of at most max_codewords + 1 rows on the host.
 
-  The cap is a stated deviation: the experiment passes
-  vec_init_num_bins = 100000, include/vtc_vq.h stops at 4096 codewords
-  (DESIGN.md 7)."""
+  max_codewords is 4096 unless the caller raises it (at most 131072): the
+  experiment passes vec_init_num_bins = 100000, and with
+  max_codewords = 131072 that call starts the fit from every distinct
+  candidate (module docstring)."""
   vectors = _vectors(vectors)
   b = vectors.shape[0]
-  m = max(1, min(int(num_bins), b, VQ_MAX_CODEWORDS))
+  max_codewords = _limit(max_codewords)
+  m = max(1, min(int(num_bins), b, max_codewords))
   # the same rows as _initial_codebook_host picks: floor(i * b / m) of m rows
   rows = (torch.arange(m, dtype=torch.int64, device=vectors.device) * b) // m
   picked = vectors.index_select(0, rows).cpu().numpy()
-  return torch.from_numpy(_initial_codebook_host(picked, m)).to(vectors.device)
+  return torch.from_numpy(
+      _initial_codebook_host(picked, m, max_codewords)).to(vectors.device)
 
 
 def vector_assign(vectors, codebook, lengths=None, lagrange_mult=0.0,
-                  return_dequantized=False):
+                  return_dequantized=False, max_codewords=VQ_MAX_CODEWORDS):
   """indices [b] int32: for every row of the (b, d) float32 device tensor the
   lowest index i < k that minimises |x - c_i|^2 + lagrange_mult * lengths[i]
   in float64, the squared distance accumulated component by component
   (include/vtc_vq.h); with lagrange_mult == 0 the nearest codeword, lengths
   unused.  Ties go to the lowest index; a row with a NaN gets -1.  With
-  return_dequantized also the (b, d) float32 codewords.  Only enqueues."""
+  return_dequantized also the (b, d) float32 codewords.  A codebook of more
+  than 4096 slots needs max_codewords (module docstring).  Only enqueues."""
   out = _vector_assign(vectors, codebook, lengths, lagrange_mult,
-                       return_dequantized)
+                       return_dequantized, max_codewords)
   return (out[0], out[1]) if return_dequantized else out[0]
 
 
 def _vector_assign(vectors, codebook, lengths, lagrange_mult,
-                   return_dequantized):
+                   return_dequantized, max_codewords=VQ_MAX_CODEWORDS):
   lib = vtc_hip.load_library()
   vectors = _vectors(vectors)
   b, d = vectors.shape
   device = vectors.device
-  values, k, own_lengths = _device_codebook(codebook, d, device)
+  values, k, own_lengths = _device_codebook(codebook, d, device, max_codewords)
   kmax = values.shape[0]
   if lengths is None:
     lengths = own_lengths
@@ -155,18 +188,19 @@ def _vector_assign(vectors, codebook, lengths, lagrange_mult,
   dequantized = (torch.empty((b, d), dtype=torch.float32, device=device)
                  if return_dequantized else None)
   status = torch.empty(1, dtype=torch.int64, device=device)
-  vtc_hip.check(lib.vtc_vq_assign(
+  assign_entry, name = _entry(lib, 'assign', kmax)
+  vtc_hip.check(assign_entry(
       vtc_hip.ptr(vectors), b, d, vtc_hip.ptr(values), vtc_hip.ptr(lengths),
       vtc_hip.ptr(k), kmax, float(lagrange_mult), vtc_hip.ptr(indices),
       vtc_hip.ptr(dequantized), vtc_hip.ptr(status),
-      vtc_hip.current_stream(device)), 'vtc_vq_assign')
+      vtc_hip.current_stream(device)), name)
   return indices, dequantized, status
 
 
-def vector_index_counts(indices, kmax):
+def vector_index_counts(indices, kmax, max_codewords=VQ_MAX_CODEWORDS):
   """int64 [kmax] device tensor: how often each index 0 .. kmax - 1 occurs in
   the [b] int32 device tensor `indices`; the -1 of a NaN row is not counted.
-  Only enqueues."""
+  kmax > 4096 needs max_codewords (module docstring).  Only enqueues."""
   lib = vtc_hip.load_library()
   indices = vtc_hip.require_device_tensor(indices, 'indices', torch.int32)
   if indices.dim() != 1 or indices.numel() == 0:
@@ -174,17 +208,22 @@ def vector_index_counts(indices, kmax):
                      % (tuple(indices.shape),))
   indices = indices.contiguous()
   kmax = int(kmax)
+  limit = max(_limit(max_codewords), VQ_MAX_CODEWORDS)
+  if kmax > limit:
+    raise NotImplementedError('kmax = %d, at most %d' % (kmax, limit))
   counts = torch.empty(max(kmax, 1), dtype=torch.int64, device=indices.device)
-  vtc_hip.check(lib.vtc_vq_index_counts(
+  counts_entry, name = _entry(lib, 'index_counts', kmax)
+  vtc_hip.check(counts_entry(
       vtc_hip.ptr(indices), indices.shape[0], kmax, vtc_hip.ptr(counts),
-      vtc_hip.current_stream(indices.device)), 'vtc_vq_index_counts')
+      vtc_hip.current_stream(indices.device)), name)
   return counts
 
 
-def vector_dequantize(indices, codebook):
+def vector_dequantize(indices, codebook, max_codewords=VQ_MAX_CODEWORDS):
   """(b, d) float32 device tensor of codebook[indices[r]] rounded once to
   float32, a row of NaN where the index is -1.  A gather: tensor plumbing done
-  by torch on the tensor's device.  Only enqueues."""
+  by torch on the tensor's device.  A codebook of more than 4096 slots needs
+  max_codewords (module docstring).  Only enqueues."""
   indices = vtc_hip.require_device_tensor(indices, 'indices', torch.int32)
   if indices.dim() != 1:
     raise ValueError('indices must be [b], got shape %s'
@@ -193,7 +232,8 @@ def vector_dequantize(indices, codebook):
     codebook = codebook['codebook']
   elif isinstance(codebook, (tuple, list)) and len(codebook) == 2:
     codebook = codebook[0]
-  values, _, _ = _device_codebook(codebook, codebook.shape[1], indices.device)
+  values, _, _ = _device_codebook(codebook, codebook.shape[1], indices.device,
+                                  max_codewords)
   picked = values.index_select(0, indices.clamp(min=0).to(torch.int64))
   picked = picked.to(torch.float32)
   return torch.where((indices < 0)[:, None],
@@ -206,7 +246,7 @@ def _state(tensors):
 
 
 def vector_lloyd(vectors, init_codebook, lagrange_mult=0.0, max_iterations=50,
-                 epsilon=1e-5, pin_zero=True):
+                 epsilon=1e-5, pin_zero=True, max_codewords=VQ_MAX_CODEWORDS):
   """An entropy-constrained vector quantiser for the rows of the (b, d)
   float32 device tensor `vectors`, fitted on the device: the twin of
   scalar_lloyd.
@@ -226,6 +266,10 @@ def vector_lloyd(vectors, init_codebook, lagrange_mult=0.0, max_iterations=50,
   device tensors (slots past k: 0.0, 0.0, 0), and, read once at the end,
   'iterations' (int), 'converged' (bool) and 'cost' float64 [3] = {J, D, R}
   of the last step (numpy).  A NaN in the vectors raises ValueError.
+
+  An init_codebook of more than 4096 rows needs max_codewords (module
+  docstring); the fit keeps its kmax slots however few stay in use, and
+  trim_vector_codebook cuts the result down to them.
   """
   lib = vtc_hip.load_library()
   vectors = _vectors(vectors)
@@ -233,7 +277,7 @@ def vector_lloyd(vectors, init_codebook, lagrange_mult=0.0, max_iterations=50,
   device = vectors.device
   if isinstance(init_codebook, dict):
     init_codebook = (init_codebook['codebook'], init_codebook['k'])
-  values, k, _ = _device_codebook(init_codebook, d, device)
+  values, k, _ = _device_codebook(init_codebook, d, device, max_codewords)
   values, k = values.clone(), k.clone()      # the fit is in place
   kmax = values.shape[0]
   # the zero codeword of the start: plumbing (comparisons) on the device
@@ -242,8 +286,8 @@ def vector_lloyd(vectors, init_codebook, lagrange_mult=0.0, max_iterations=50,
   zero = torch.where(is_zero.any(), is_zero.to(torch.int32).argmax(),
                      torch.tensor(-1, device=device)).to(torch.int32)
   indices, _, first_status = _vector_assign(vectors, (values, k), None, 0.0,
-                                            False)
-  counts = vector_index_counts(indices, kmax)
+                                            False, max_codewords)
+  counts = vector_index_counts(indices, kmax, max_codewords)
   del indices
   # the first step's input lengths, by torch (module docstring)
   lengths = -torch.log2(counts.to(torch.float64) /
@@ -256,15 +300,16 @@ def vector_lloyd(vectors, init_codebook, lagrange_mult=0.0, max_iterations=50,
       'iterations': torch.zeros(1, dtype=torch.int32, device=device)}
   state = _state(tensors)
   status = torch.zeros(1, dtype=torch.int64, device=device)
-  ws = vtc_hip.workspace(lib.vtc_vq_lloyd_step_workspace_bytes(b, d, kmax),
-                         device)
+  step_bytes, _ = _entry(lib, 'lloyd_step_workspace_bytes', kmax)
+  step_entry, step_name = _entry(lib, 'lloyd_step', kmax)
+  ws = vtc_hip.workspace(step_bytes(b, d, kmax), device)
   stream = vtc_hip.current_stream(device)
   for _ in range(int(max_iterations)):
-    vtc_hip.check(lib.vtc_vq_lloyd_step(
+    vtc_hip.check(step_entry(
         vtc_hip.ptr(vectors), b, d, kmax, float(lagrange_mult),
         float(epsilon), 1 if pin_zero else 0, ctypes.byref(state),
         ctypes.byref(state), vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
-        stream), 'vtc_vq_lloyd_step')
+        stream), step_name)
   # the one read: everything as float64 in one buffer (module docstring)
   tail = torch.cat([tensors['active'].to(torch.float64),
                     tensors['iterations'].to(torch.float64),
@@ -278,6 +323,40 @@ def vector_lloyd(vectors, init_codebook, lagrange_mult=0.0, max_iterations=50,
   result['converged'] = bool(tail[0] == 0)
   result['cost'] = tail[2:5].copy()
   return result
+
+
+def trim_vector_codebook(result):
+  """The quantiser of vector_lloyd's dictionary `result` with kmax = k: the
+  slots in use of 'codebook', 'lengths' and 'counts' (copies), every other
+  entry as it is.  It assigns exactly as `result` does, since the slots past k
+  are never read.  A fit that started above 4096 codewords and ended at or
+  below them is thereby handed to everything that takes at most 4096, the
+  Huffman and range coders of the indices included.  One host read (k)."""
+  k = int(result['k'].reshape(-1)[0])
+  trimmed = dict(result)
+  for name in ('codebook', 'lengths', 'counts'):
+    trimmed[name] = result[name][:k].clone()
+  trimmed['k'] = result['k'].clone()
+  return trimmed
+
+
+def _slots(codebook):
+  """kmax of a codebook in any of the accepted forms, without touching it."""
+  if isinstance(codebook, dict):
+    codebook = codebook['codebook']
+  elif isinstance(codebook, (tuple, list)) and len(codebook) == 2:
+    codebook = codebook[0]
+  return int(codebook.shape[0])
+
+
+def _check_table_code(source_code, vec_codebook):
+  if (source_code in _scalar._TABLE_CODES and
+      _slots(vec_codebook) > VQ_MAX_CODEWORDS):
+    raise NotImplementedError(
+        "source_code %r codes at most %d symbols and the vector codebook has "
+        "kmax = %d slots: cut a fit that ended at k <= %d down with "
+        "trim_vector_codebook" % (source_code, VQ_MAX_CODEWORDS,
+                                  _slots(vec_codebook), VQ_MAX_CODEWORDS))
 
 
 # ------------------------------------------------------------- rate-distortion
@@ -296,7 +375,8 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                            vec_lengths=None, vec_lagrange_mult=0.0,
                            fullimg_reshape_params=None, source_code='entropy',
                            tables=None, from_stream=False,
-                           rows_per_stream=None):
+                           rows_per_stream=None,
+                           vec_max_codewords=VQ_MAX_CODEWORDS):
   """One rate-distortion point of codes quantised in two parts.
 
   codes : (b, s) float32 device tensor; patches : (b, n); dictionary : (s, n),
@@ -334,9 +414,14 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   that index array is packed with index_coding.pack_index_streams
   (pack_index_ans) and read back by decode_codes_mixed; reconstruction and
   distortion are those of the decoded codes and the rate is the streams' total
-  bits / patches.numel()."""
+  bits / patches.numel().
+
+  vec_max_codewords: a vec_codebook of more than 4096 slots needs it (module
+  docstring), and then source_code must be 'entropy': the table codes raise
+  NotImplementedError before any device work."""
   _scalar._check_source_code(source_code)
   _scalar._check_from_stream(from_stream, source_code)
+  _check_table_code(source_code, vec_codebook)
   codes = _scalar._codes(codes)
   patches = _scalar._codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
@@ -357,12 +442,12 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
       codes.index_select(1, scal_at).contiguous(), scal_pair, scal_lengths,
       scal_lagrange_mult, True)
   vec_values, vec_k, own_lengths = _device_codebook(vec_codebook, len(vec),
-                                                    device)
+                                                    device, vec_max_codewords)
   if vec_lengths is None:
     vec_lengths = own_lengths
   vec_indices, vec_deq, vec_status = _vector_assign(
       codes.index_select(1, vec_at).contiguous(), (vec_values, vec_k),
-      vec_lengths, vec_lagrange_mult, True)
+      vec_lengths, vec_lagrange_mult, True, vec_max_codewords)
 
   dequantized = torch.zeros((b, s), dtype=torch.float32, device=device)
   dequantized.index_copy_(1, scal_at, scal_deq)
@@ -416,8 +501,8 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   else:
     total_bits = (
         entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
-        entropy_bits(vector_index_counts(vec_indices,
-                                         vec_values.shape[0])[None, :]))
+        entropy_bits(vector_index_counts(vec_indices, vec_values.shape[0],
+                                         vec_max_codewords)[None, :]))
   rate = total_bits / float(patches.numel())
   distortion = _scalar._distortion(patches, reconstruction,
                                    fullimg_reshape_params)
@@ -491,12 +576,19 @@ def _gathered(codes, cluster):
 
 
 def _fit_vector_part(codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
-                     max_iterations, epsilon):
+                     max_iterations, epsilon, source_code, max_codewords):
+  """(the dictionary of vector_lloyd, its 'lengths').  A fit of more than 4096
+  slots that a table code is to follow is cut down to its slots in use."""
   vectors = _gathered(codes, vec_clust)
-  return vector_lloyd(vectors,
-                      initial_vector_codebook(vectors, vec_init_num_bins),
-                      lagrange_mult=vec_quant_multiplier,
-                      max_iterations=max_iterations, epsilon=epsilon)
+  fitted = vector_lloyd(
+      vectors,
+      initial_vector_codebook(vectors, vec_init_num_bins, max_codewords),
+      lagrange_mult=vec_quant_multiplier, max_iterations=max_iterations,
+      epsilon=epsilon, max_codewords=max_codewords)
+  if (source_code in _scalar._TABLE_CODES and
+      _slots(fitted) > VQ_MAX_CODEWORDS):
+    fitted = trim_vector_codebook(fitted)
+  return fitted, fitted['lengths']
 
 
 def _mixed_point(who, training, source_code, from_stream, rows_per_stream,
@@ -528,7 +620,8 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
                           epsilon=1e-5, source_code='entropy',
-                          from_stream=False, rows_per_stream=None):
+                          from_stream=False, rows_per_stream=None,
+                          vec_max_codewords=VQ_MAX_CODEWORDS):
   """The experiment's Mod2_compute_RD_point, with (b, s) codes (module
   docstring): the columns scal_clusts get uniform scalar codebooks of bin
   width scal_binwidths * scal_quant_multiplier (as in
@@ -555,14 +648,23 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   the test indices under them.  Precomputed codebooks without both tables
   raise ValueError.  from_stream is that of compute_RD_point_mixed, and so
   are source_code='ans' and rows_per_stream: huff_tab1 and huff_tab2 are then
-  the scalar and the vector frequency arrays."""
+  the scalar and the vector frequency arrays.
+
+  vec_max_codewords (4096, at most 131072) goes to initial_vector_codebook,
+  vector_lloyd and compute_RD_point_mixed: with vec_max_codewords=131072 the
+  experiment's vec_init_num_bins=100000 starts the fit from every distinct
+  candidate.  The returned vec_cbook keeps the slots it started with;
+  source_code 'huffman' and 'ans' code at most 4096 symbols, so a training
+  call under them cuts a larger fit down with trim_vector_codebook first and
+  raises NotImplementedError only if more than 4096 codewords are still in
+  use."""
   training = precomputed_scal_codebook is None
   if training:
     scal_cbook = _scalar._uniform_for(_gathered(codes, scal_clusts),
                                       scal_binwidths, scal_quant_multiplier)
-    vec_cbook = _fit_vector_part(codes, vec_clust, vec_quant_multiplier,
-                                 vec_init_num_bins, max_iterations, epsilon)
-    vec_cw_len = vec_cbook['lengths']
+    vec_cbook, vec_cw_len = _fit_vector_part(
+        codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
+        max_iterations, epsilon, source_code, vec_max_codewords)
   else:
     scal_cbook, vec_cbook, vec_cw_len = (precomputed_scal_codebook,
                                          precomputed_vec_codebook,
@@ -574,7 +676,8 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
       codes, patches, dictionary, scal_clusts, scal_cbook, vec_clust,
       vec_cbook, vec_lengths=vec_cw_len,
       vec_lagrange_mult=vec_quant_multiplier,
-      fullimg_reshape_params=fullimg_reshape_params)
+      fullimg_reshape_params=fullimg_reshape_params,
+      vec_max_codewords=vec_max_codewords)
   if training:
     return (rate, distortion, scal_cbook, vec_cbook, vec_cw_len, huff_tab1,
             huff_tab2, None)
@@ -592,7 +695,8 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
                           precomputed_huff_tab3=None,
                           fullimg_reshape_params=None, max_iterations=50,
                           epsilon=1e-5, source_code='entropy',
-                          from_stream=False, rows_per_stream=None):
+                          from_stream=False, rows_per_stream=None,
+                          vec_max_codewords=VQ_MAX_CODEWORDS):
   """The experiment's Mod3_compute_RD_point: Mod2_compute_RD_point with
   entropy-constrained scalar quantisers, scalar_lloyd from uniform codebooks
   of bin width scal_binwidths with lagrange_mult = scal_quant_multiplier (as
@@ -600,8 +704,8 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   scalar multiplier again, so the returned scal_cbook is scalar_lloyd's
   dictionary with one more key, 'lagrange_mult', and a test call assigns with
   that value and the dictionary's 'lengths'.  Returns as Mod2_compute_RD_point
-  does, source_code='huffman' and 'ans', their table slots, from_stream and
-  rows_per_stream included."""
+  does, source_code='huffman' and 'ans', their table slots, from_stream,
+  rows_per_stream and vec_max_codewords included."""
   training = precomputed_scal_codebook is None
   if training:
     scal_codes = _gathered(codes, scal_clusts)
@@ -610,9 +714,9 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
         lagrange_mult=scal_quant_multiplier, max_iterations=max_iterations,
         epsilon=epsilon)
     scal_cbook['lagrange_mult'] = scal_quant_multiplier
-    vec_cbook = _fit_vector_part(codes, vec_clust, vec_quant_multiplier,
-                                 vec_init_num_bins, max_iterations, epsilon)
-    vec_cw_len = vec_cbook['lengths']
+    vec_cbook, vec_cw_len = _fit_vector_part(
+        codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
+        max_iterations, epsilon, source_code, vec_max_codewords)
   else:
     scal_cbook, vec_cbook, vec_cw_len = (precomputed_scal_codebook,
                                          precomputed_vec_codebook,
@@ -625,7 +729,8 @@ def Mod3_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
       vec_cbook, scal_lengths=scal_cbook['lengths'],
       scal_lagrange_mult=scal_cbook['lagrange_mult'], vec_lengths=vec_cw_len,
       vec_lagrange_mult=vec_quant_multiplier,
-      fullimg_reshape_params=fullimg_reshape_params)
+      fullimg_reshape_params=fullimg_reshape_params,
+      vec_max_codewords=vec_max_codewords)
   if training:
     return (rate, distortion, scal_cbook, vec_cbook, vec_cw_len, huff_tab1,
             huff_tab2, None)

@@ -342,6 +342,23 @@ INDEX_ANS_SIGNATURES = {
                                     _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+VQ_LARGE_ABI_VERSION = 1   # VTC_VQ_LARGE_ABI_VERSION of vtc_vq_large.h
+VQ_LARGE_MAX_CODEWORDS = 131072   # VTC_VQ_LARGE_MAX_CODEWORDS
+
+# The twelfth header, include/vtc_vq_large.h (same library): the vector
+# quantiser of the eighth for up to 131 072 codewords, the same argument lists
+# and struct vtc_vq_state.  Again a table of its own.
+VQ_LARGE_SIGNATURES = {
+    'vtc_vq_large_abi_version': (_i32, []),
+    'vtc_vq_large_assign': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _f64,
+                                   _vp, _vp, _vp, _vp]),
+    'vtc_vq_large_lloyd_step_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'vtc_vq_large_lloyd_step': (_i32, [_vp, _i64, _i32, _i32, _f64, _f64,
+                                       _i32, _VQSTATE_P, _VQSTATE_P, _vp, _vp,
+                                       _sz, _vp]),
+    'vtc_vq_large_index_counts': (_i32, [_vp, _i64, _i32, _vp, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -361,7 +378,8 @@ def load_library():
   for table in (SIGNATURES, IMAGE_SIGNATURES, CODEC_SIGNATURES,
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
                 QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
-                INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES):
+                INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES,
+                VQ_LARGE_SIGNATURES):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -388,6 +406,9 @@ def load_library():
     raise ImportError('libvtc_hip.so index decode ABI version mismatch')
   if lib.vtc_index_ans_abi_version() != INDEX_ANS_ABI_VERSION:
     raise ImportError('libvtc_hip.so index ANS ABI version mismatch')
+  if lib.vtc_vq_large_abi_version() != VQ_LARGE_ABI_VERSION:
+    raise ImportError('libvtc_hip.so large vector quantiser ABI version '
+                      'mismatch')
   _lib = lib
   return lib
 
