@@ -29,12 +29,25 @@ include/vtc_index_ans.h does not:
                          rows_per_stream), offsets in BYTES, one per stream
   unpack_index_ans       (packed, offsets), freq, b, rows_per_stream -> indices
 
+The 15-bit tables of that coder stop at 4096 symbols a column.  The index of
+the large vector quantiser (up to 131 072 codewords) is one column, coded as
+two symbols, i >> 8 and i & 255, under the same states
+(include/ext/vtc_index_ans_split.h):
+
+  index_ans_split_frequencies   counts [kmax] -> (freq_hi uint16 [H], freq_lo
+                                uint16 (H, 256)), H = ceil(kmax / 256)
+  index_ans_split_stream_bytes  indices [b], tables -> bytes of every stream
+  pack_index_ans_split          indices [b], tables -> (packed, offsets,
+                                rows_per_stream)
+  unpack_index_ans_split        (packed, offsets), tables, b, rows_per_stream
+                                -> indices [b]
+
 The per-entry work runs in the kernels of csrc/index_code.hip behind
 include/vtc_index_code.h, for the way back of
 csrc/index_decode.hip behind include/vtc_index_decode.h, and
-of csrc/index_ans.hip.  Indices are (b, m) int32 device tensors: m index
-streams ("columns") per row, each with a table of its own, {int index: str of
-'0' / '1'}, or a row of frequencies.
+of csrc/index_ans.hip and csrc/index_ans_split.hip.  Indices are (b, m) int32
+device tensors: m index streams ("columns") per row, each with a table of its
+own, {int index: str of '0' / '1'}, or a row of frequencies.
 """
 import numpy as np
 import torch
@@ -335,35 +348,43 @@ def index_ans_frequencies(counts, k=None):
       k = k * m
   if len(k) != m or min(k) < 1 or max(k) > kmax:
     raise ValueError('k must hold %d values in [1, %d]' % (m, kmax))
-  scale = 1 << ANS_PROB_BITS
   freq = np.zeros((m, kmax), dtype=np.uint16)
   for j, row in enumerate(rows):
     kj = k[j]
     if min(row[:kj]) < 0:
       raise ValueError('column %d has a negative count' % j)
-    w = [c if c > 0 else 1 for c in row[:kj]]
-    total = sum(w)
-    f = [max(1, (wi << ANS_PROB_BITS) // total) for wi in w]
-    order = sorted(range(kj), key=lambda i: (-w[i], i))
-    d = scale - sum(f)
-    # one unit at a time round the order, whole rounds taken at once
-    if d > 0:
-      rounds, rest = divmod(d, kj)
-      for rank, i in enumerate(order):
-        f[i] += rounds + (1 if rank < rest else 0)
-    while d < 0:
-      open_ = [i for i in order if f[i] > 1]   # not empty: sum f > 2^15 >= k
-      rounds = min(-d // len(open_), min(f[i] for i in open_) - 1)
-      if rounds:
-        for i in open_:
-          f[i] -= rounds
-        d += rounds * len(open_)
-      else:                                    # a last, partial round
-        for i in open_[:-d]:
-          f[i] -= 1
-        d = 0
-    freq[j, :kj] = f
+    freq[j, :kj] = _ans_weights_to_frequencies(
+        [c if c > 0 else 1 for c in row[:kj]])
   return freq
+
+
+def _ans_weights_to_frequencies(w):
+  """Steps 2 and 3 of the rule of index_ans_frequencies for the positive
+  weights w of the symbols in use: as many frequencies, >= 1, summing to
+  2^15."""
+  scale = 1 << ANS_PROB_BITS
+  kj = len(w)
+  total = sum(w)
+  f = [max(1, (wi << ANS_PROB_BITS) // total) for wi in w]
+  order = sorted(range(kj), key=lambda i: (-w[i], i))
+  d = scale - sum(f)
+  # one unit at a time round the order, whole rounds taken at once
+  if d > 0:
+    rounds, rest = divmod(d, kj)
+    for rank, i in enumerate(order):
+      f[i] += rounds + (1 if rank < rest else 0)
+  while d < 0:
+    open_ = [i for i in order if f[i] > 1]   # not empty: sum f > 2^15 >= k
+    rounds = min(-d // len(open_), min(f[i] for i in open_) - 1)
+    if rounds:
+      for i in open_:
+        f[i] -= rounds
+      d += rounds * len(open_)
+    else:                                    # a last, partial round
+      for i in open_[:-d]:
+        f[i] -= 1
+      d = 0
+  return f
 
 
 def _ans_freq(freq, m, device):
@@ -532,5 +553,251 @@ def unpack_index_ans(packed, offsets, freq, b, rows_per_stream, exact=True):
   if exact and loose:
     raise ValueError('unpack_index_ans: %d streams of %d do not use up their '
                      'span of bytes, the first is stream %d'
+                     % (loose, n, first_loose))
+  return indices
+
+
+# ------------------------------------- range coding, more than 4096 symbols
+ANS_SPLIT_MAX_SYMBOLS = vtc_hip.INDEX_ANS_SPLIT_MAX_SYMBOLS
+ANS_SPLIT_LO_SYMBOLS = 1 << vtc_hip.INDEX_ANS_SPLIT_LO_BITS
+ANS_SPLIT_ROWS = 65536   # rows of a stream when the caller names none
+
+
+def index_ans_split_frequencies(counts, k=None):
+  """(freq_hi uint16 [H], freq_lo uint16 (H, 256)) numpy arrays, H =
+  ceil(kmax / 256): the tables of the split range coder
+  (include/ext/vtc_index_ans_split.h) from the [kmax] counts of one index column
+  (vector_quantization.vector_index_counts) and the codewords in use k (None
+  for kmax).  On the host, Python integers only:
+
+  1. the weight w_i is count_i, or 1 when count_i = 0, for i < k; 0 from k on;
+  2. row h of freq_lo: the rule of index_ans_frequencies on the counts of
+     block h (indices 256 h .. 256 h + 255) with k_h = clamp(k - 256 h, 0,
+     256) symbols in use; a row with k_h = 0 is all zero;
+  3. freq_hi: steps 2 and 3 of that rule on the block weights W_h = sum of the
+     w_i of block h, for the ceil(k / 256) blocks in use; 0 beyond.
+
+  Every index below k stays codable.  NotImplementedError for kmax >
+  131072."""
+  if (isinstance(counts, (list, tuple)) and counts and
+      not hasattr(counts[0], '__len__')):
+    counts = [counts]          # a plain row of Python integers
+  rows = _host_rows(counts)
+  if len(rows) != 1:
+    raise ValueError('counts must hold one column, got %d' % len(rows))
+  row = rows[0]
+  kmax = len(row)
+  if kmax > ANS_SPLIT_MAX_SYMBOLS:
+    raise NotImplementedError('kmax = %d, at most %d'
+                              % (kmax, ANS_SPLIT_MAX_SYMBOLS))
+  if k is None:
+    k = kmax
+  else:
+    if torch.is_tensor(k):
+      k = k.cpu().numpy()
+    k = np.asarray(k).reshape(-1)
+    if len(k) != 1:
+      raise ValueError('k must be one value')
+    k = int(k[0])
+  if not 1 <= k <= kmax:
+    raise ValueError('k must lie in [1, %d]' % kmax)
+  if min(row[:k]) < 0:
+    raise ValueError('the column has a negative count')
+  lo = ANS_SPLIT_LO_SYMBOLS
+  top = -(-kmax // lo)
+  freq_hi = np.zeros(top, dtype=np.uint16)
+  freq_lo = np.zeros((top, lo), dtype=np.uint16)
+  block_weights = []
+  for h in range(-(-k // lo)):
+    w = [c if c > 0 else 1 for c in row[lo * h:min(k, lo * (h + 1))]]
+    freq_lo[h, :len(w)] = _ans_weights_to_frequencies(w)
+    block_weights.append(sum(w))
+  freq_hi[:len(block_weights)] = _ans_weights_to_frequencies(block_weights)
+  return freq_hi, freq_lo
+
+
+def _ans_split_tables(tables, device):
+  """(freq_hi, freq_lo) as device tensors of int16 bit patterns, and the kmax
+  the calls are given: 256 H, every symbol the tables can hold."""
+  try:
+    freq_hi, freq_lo = tables
+  except (TypeError, ValueError):
+    raise ValueError('tables must be the pair (freq_hi, freq_lo)')
+  host = []
+  for freq in (freq_hi, freq_lo):
+    if torch.is_tensor(freq):
+      freq = freq.cpu().numpy()
+    host.append(np.asarray(freq))
+  freq_hi, freq_lo = host
+  lo = ANS_SPLIT_LO_SYMBOLS
+  if (freq_hi.dtype != np.uint16 or freq_lo.dtype != np.uint16 or
+      freq_hi.ndim != 1 or freq_hi.shape[0] < 1 or
+      freq_lo.shape != (freq_hi.shape[0], lo)):
+    raise ValueError('tables must be uint16 arrays [H] and (H, %d)' % lo)
+  top = freq_hi.shape[0]
+  if top * lo > ANS_SPLIT_MAX_SYMBOLS:
+    raise NotImplementedError('kmax = %d, at most %d'
+                              % (top * lo, ANS_SPLIT_MAX_SYMBOLS))
+  scale = 1 << ANS_PROB_BITS
+  if int(freq_hi.astype(np.int64).sum()) != scale:
+    raise ValueError('the hi frequencies sum to %d, not 2^%d'
+                     % (int(freq_hi.astype(np.int64).sum()), ANS_PROB_BITS))
+  sums = freq_lo.astype(np.int64).sum(1)
+  wrong = np.nonzero((sums != scale) & (freq_hi > 0))[0]
+  if len(wrong):
+    raise ValueError('the lo frequencies of row %d sum to %d, not 2^%d'
+                     % (wrong[0], sums[wrong[0]], ANS_PROB_BITS))
+  return (torch.from_numpy(np.ascontiguousarray(freq_hi).view(np.int16))
+          .to(device),
+          torch.from_numpy(np.ascontiguousarray(freq_lo).view(np.int16))
+          .to(device), top * lo)
+
+
+def _ans_split_column(indices):
+  indices = vtc_hip.require_device_tensor(indices, 'indices', torch.int32)
+  if indices.dim() == 2 and indices.shape[1] == 1:
+    indices = indices[:, 0]
+  if indices.dim() != 1 or indices.numel() == 0:
+    raise ValueError('indices must be [b], one column, got shape %s'
+                     % (tuple(indices.shape),))
+  return indices.contiguous()
+
+
+def _ans_split_rows(rows_per_stream):
+  if rows_per_stream is None:
+    return ANS_SPLIT_ROWS
+  rows = int(rows_per_stream)
+  if rows < 1 or rows > ANS_MAX_STREAM_SYMBOLS:
+    raise ValueError('rows_per_stream = %d: at least 1 and at most %d symbols '
+                     'in a stream' % (rows, ANS_MAX_STREAM_SYMBOLS))
+  return rows
+
+
+def _ans_split_bad(what, bad):
+  # _ans_split_tables saw the same tables
+  if bad == 1:
+    raise ValueError('%s: the hi frequencies do not sum to 2^%d'
+                     % (what, ANS_PROB_BITS))
+  raise ValueError('%s: the lo frequencies of row %d do not sum to 2^%d or '
+                   'are not 0 from kmax on' % (what, bad - 2, ANS_PROB_BITS))
+
+
+def _raise_ans_split_status(indices, status, what):
+  uncodable, first, bad = status.tolist()
+  if bad:
+    _ans_split_bad(what, bad)
+  if uncodable:
+    raise KeyError('%s: no frequency for index %d (row %d); %d such entries'
+                   % (what, int(indices[first - 1]), first - 1, uncodable))
+
+
+def _ans_split_sizes(lib, indices, tables, rows, ws, status):
+  freq_hi, freq_lo, kmax = tables
+  b, device = indices.shape[0], indices.device
+  sizes = torch.empty(-(-b // rows), dtype=torch.int32, device=device)
+  vtc_hip.check(lib.vtc_index_ans_split_sizes(
+      vtc_hip.ptr(indices), b, vtc_hip.ptr(freq_hi), vtc_hip.ptr(freq_lo),
+      kmax, rows, vtc_hip.ptr(sizes), vtc_hip.ptr(status), vtc_hip.ptr(ws),
+      ws.numel(), vtc_hip.current_stream(device)),
+                'vtc_index_ans_split_sizes')
+  return sizes
+
+
+def index_ans_split_stream_bytes(indices, tables, rows_per_stream=None):
+  """int32 device tensor [ceil(b / rows_per_stream)]: the bytes of every
+  stream of the [b] indices under tables = (freq_hi, freq_lo), 256 of end
+  states and two per word.  rows_per_stream defaults to 65536.  One host read
+  (the status).  An index without a frequency (the -1 of a NaN code among
+  them) raises KeyError naming its row and the index; tables whose sums are
+  not 2^15 raise ValueError before any device work."""
+  lib = vtc_hip.load_library()
+  indices = _ans_split_column(indices)
+  device = indices.device
+  rows = _ans_split_rows(rows_per_stream)
+  tables = _ans_split_tables(tables, device)
+  ws = vtc_hip.workspace(
+      lib.vtc_index_ans_split_workspace_bytes(tables[2]), device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  sizes = _ans_split_sizes(lib, indices, tables, rows, ws, status)
+  _raise_ans_split_status(indices, status, 'index_ans_split_stream_bytes')
+  return sizes
+
+
+def pack_index_ans_split(indices, tables, rows_per_stream=None):
+  """(packed, offsets, rows_per_stream) of the [b] indices under tables =
+  (freq_hi, freq_lo): what pack_index_ans returns, for the streams of
+  include/ext/vtc_index_ans_split.h."""
+  lib = vtc_hip.load_library()
+  indices = _ans_split_column(indices)
+  b, device = indices.shape[0], indices.device
+  rows = _ans_split_rows(rows_per_stream)
+  tables = _ans_split_tables(tables, device)
+  freq_hi, freq_lo, kmax = tables
+  ws = vtc_hip.workspace(lib.vtc_index_ans_split_workspace_bytes(kmax), device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  sizes = _ans_split_sizes(lib, indices, tables, rows, ws, status)
+  _raise_ans_split_status(indices, status, 'pack_index_ans_split')
+  offsets = jpeg.bit_offsets(sizes)   # a plain prefix sum: bytes here
+  total = int(offsets[-1])
+  packed = torch.empty(total, dtype=torch.uint8, device=device)
+  vtc_hip.check(lib.vtc_index_ans_split_pack(
+      vtc_hip.ptr(indices), b, vtc_hip.ptr(freq_hi), vtc_hip.ptr(freq_lo),
+      kmax, rows, vtc_hip.ptr(sizes), vtc_hip.ptr(offsets),
+      vtc_hip.ptr(packed), total, vtc_hip.ptr(status), vtc_hip.ptr(ws),
+      ws.numel(), vtc_hip.current_stream(device)), 'vtc_index_ans_split_pack')
+  skipped = int(status[2])
+  if skipped:
+    raise ValueError('pack_index_ans_split: %d streams outside the output'
+                     % skipped)
+  return packed, offsets, rows
+
+
+def unpack_index_ans_split(packed, offsets, tables, b, rows_per_stream,
+                           exact=True):
+  """indices [b] int32 device tensor from what pack_index_ans_split returns.
+  Errors are those of unpack_index_ans: ValueError for bad sums (before any
+  device work), for malformed streams and, with exact=True, for streams that
+  leave bytes of their span unread; VtcHipError for a CPU tensor.  One host
+  read."""
+  packed = vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
+  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
+  b = int(b)
+  if b < 1:
+    raise ValueError('b must be at least 1')
+  rows = _ans_split_rows(rows_per_stream)
+  n = -(-b // rows)
+  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] != n + 1:
+    raise ValueError('packed must be (bytes,) and offsets (%d,) for %d rows in '
+                     'streams of %d, got shapes %s and %s'
+                     % (n + 1, b, rows, tuple(packed.shape),
+                        tuple(offsets.shape)))
+  lib = vtc_hip.load_library()
+  packed, offsets = packed.contiguous(), offsets.contiguous()
+  device = packed.device
+  freq_hi, freq_lo, kmax = _ans_split_tables(tables, device)
+  indices = torch.empty(b, dtype=torch.int32, device=device)
+  used = torch.empty(n, dtype=torch.int32, device=device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  ws = vtc_hip.workspace(lib.vtc_index_ans_split_workspace_bytes(kmax), device)
+  bytes_from = packed if packed.numel() else ws   # never read when empty
+  vtc_hip.check(lib.vtc_index_ans_split_unpack(
+      vtc_hip.ptr(bytes_from), packed.numel(), vtc_hip.ptr(offsets), b,
+      vtc_hip.ptr(freq_hi), vtc_hip.ptr(freq_lo), kmax, rows,
+      vtc_hip.ptr(indices), vtc_hip.ptr(used), vtc_hip.ptr(status),
+      vtc_hip.ptr(ws), ws.numel(), vtc_hip.current_stream(device)),
+                'vtc_index_ans_split_unpack')
+  loose = used.to(torch.int64) != offsets[1:] - offsets[:-1]
+  report = torch.cat([status, torch.stack([
+      loose.sum(), loose.to(torch.int32).argmax().to(torch.int64)])])
+  malformed, first, bad, loose, first_loose = report.tolist()
+  if bad:
+    _ans_split_bad('unpack_index_ans_split', bad)
+  if malformed:
+    raise ValueError('unpack_index_ans_split: %d malformed streams of %d, the '
+                     'first is stream %d (rows %d and on)'
+                     % (malformed, n, first - 1, (first - 1) * rows))
+  if exact and loose:
+    raise ValueError('unpack_index_ans_split: %d streams of %d do not use up '
+                     'their span of bytes, the first is stream %d'
                      % (loose, n, first_loose))
   return indices

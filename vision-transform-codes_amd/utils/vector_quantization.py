@@ -21,6 +21,8 @@ DESIGN.md 4.20), which return the same bits where both apply, and a larger one
 raises NotImplementedError naming the limit in force.  Index coding stops at
 4096 symbols: source_code 'huffman' and 'ans' need a vector codebook of at most
 4096 slots, which trim_vector_codebook makes of a fit that ended there.
+source_code 'ans_split' codes the vector index under the split range coder of
+include/ext/vtc_index_ans_split.h instead, whatever the codebook's size.
 
 A vector quantiser of (b, d) vectors is described by
   codebook   float64 (kmax, d)  the codewords; the slots past k are never read
@@ -359,6 +361,19 @@ def _check_table_code(source_code, vec_codebook):
                                   _slots(vec_codebook), VQ_MAX_CODEWORDS))
 
 
+# the source code of compute_RD_point_mixed, Mod2 and Mod3 alone: the scalar
+# columns under the range coder, the vector index under the split range coder
+# of include/ext/vtc_index_ans_split.h, which takes up to 131 072 symbols
+_SPLIT_CODE = 'ans_split'
+
+
+def _check_mixed_source_code(source_code, from_stream):
+  if source_code == _SPLIT_CODE:
+    return
+  _scalar._check_source_code(source_code)
+  _scalar._check_from_stream(from_stream, source_code)
+
+
 # ------------------------------------------------------------- rate-distortion
 def _cluster(cluster, s, name):
   cluster = [int(c) for c in cluster]
@@ -416,11 +431,21 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   distortion are those of the decoded codes and the rate is the streams' total
   bits / patches.numel().
 
+  source_code 'ans_split': the scalar indices (b, len(scal_clusts)) go through
+  the range coder as under 'ans', and the vector index through the split range
+  coder of include/ext/vtc_index_ans_split.h (index_coding.pack_index_ans_split)
+  as a stream set of its own, which takes up to 131072 symbols.  `tables` =
+  (scalar frequencies uint16 (len(scal_clusts), kmax), (freq_hi, freq_lo)),
+  trained on these indices when None (index_ans_frequencies,
+  index_ans_split_frequencies) and returned as the third value.  The rate is
+  8 x the bytes of both stream sets / patches.numel(); rows_per_stream applies
+  to both, and None means each coder's default.  from_stream decodes both with
+  decode_codes_mixed_split.
+
   vec_max_codewords: a vec_codebook of more than 4096 slots needs it (module
-  docstring), and then source_code must be 'entropy': the table codes raise
-  NotImplementedError before any device work."""
-  _scalar._check_source_code(source_code)
-  _scalar._check_from_stream(from_stream, source_code)
+  docstring), and then source_code must be 'entropy' or 'ans_split': 'huffman'
+  and 'ans' raise NotImplementedError before any device work."""
+  _check_mixed_source_code(source_code, from_stream)
   _check_table_code(source_code, vec_codebook)
   codes = _scalar._codes(codes)
   patches = _scalar._codes(patches, 'patches')
@@ -498,6 +523,32 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
     else:
       total_bits, _ = _scalar._ans_bits(streams, all_tables, None,
                                         rows_per_stream)
+  elif source_code == _SPLIT_CODE:
+    from utils import index_coding
+    if tables is None:
+      tables = (
+          index_coding.index_ans_frequencies(
+              index_counts(scal_indices, scal_pair[0].shape[1]), scal_pair[1]),
+          index_coding.index_ans_split_frequencies(
+              vector_index_counts(vec_indices, vec_values.shape[0],
+                                  vec_max_codewords), vec_k))
+    scalar_tables, vector_table = tables
+    if from_stream:
+      scal_streams = index_coding.pack_index_ans(scal_indices, scalar_tables,
+                                                 rows_per_stream)
+      vec_streams = index_coding.pack_index_ans_split(
+          vec_indices, vector_table, rows_per_stream)
+      total_bits = 8 * (int(scal_streams[1][-1]) + int(vec_streams[1][-1]))
+      reconstruction = _scalar._reconstruct(
+          decode_codes_mixed_split(
+              scal_streams, vec_streams, tables, scal, scal_pair, vec,
+              (vec_values, vec_k), s, b, vec_max_codewords), dictionary)
+    else:
+      total_bits = 8 * (
+          int(index_coding.index_ans_stream_bytes(
+              scal_indices, scalar_tables, rows_per_stream).sum()) +
+          int(index_coding.index_ans_split_stream_bytes(
+              vec_indices, vector_table, rows_per_stream).sum()))
   else:
     total_bits = (
         entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
@@ -508,7 +559,7 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
                                    fullimg_reshape_params)
   if source_code == 'huffman':
     return rate, distortion, (list(scalar_tables), vector_table)
-  if source_code == 'ans':
+  if source_code in ('ans', _SPLIT_CODE):
     return rate, distortion, (scalar_tables, vector_table)
   return rate, distortion
 
@@ -568,6 +619,49 @@ def decode_codes_mixed(packed, offsets, tables, scal_clusts, scal_codebooks,
   return codes
 
 
+def decode_codes_mixed_split(scalar_streams, vector_streams, tables,
+                             scal_clusts, scal_codebooks, vec_clust,
+                             vec_codebook, s, b,
+                             vec_max_codewords=VQ_MAX_CODEWORDS):
+  """The (b, s) float32 dequantised codes of the two stream sets that
+  compute_RD_point_mixed writes under source_code='ans_split':
+  scalar_streams = (packed, offsets, rows_per_stream) of
+  index_coding.pack_index_ans for the (b, len(scal_clusts)) scalar indices,
+  vector_streams the same of index_coding.pack_index_ans_split for the [b]
+  vector indices, tables = (scalar frequencies, (freq_hi, freq_lo)).  Then
+  quantization.dequantize_assignments into the columns scal_clusts and
+  vector_dequantize (with vec_max_codewords) into the columns vec_clust; a
+  column in neither cluster is zero.  Two host reads (the decoders'
+  statuses)."""
+  from utils import index_coding
+  s, b = int(s), int(b)
+  scal = _cluster(scal_clusts, s, 'scal_clusts')
+  vec = _cluster(vec_clust, s, 'vec_clust')
+  if len(set(scal + vec)) != len(scal) + len(vec):
+    raise ValueError('scal_clusts and vec_clust overlap')
+  scalar_tables, vector_table = tables
+  if len(scalar_tables) != len(scal):
+    raise ValueError('%d rows of frequencies for %d scalar columns'
+                     % (len(scalar_tables), len(scal)))
+  scal_indices = index_coding.unpack_index_ans(
+      scalar_streams[0], scalar_streams[1], scalar_tables, b,
+      scalar_streams[2])
+  vec_indices = index_coding.unpack_index_ans_split(
+      vector_streams[0], vector_streams[1], vector_table, b,
+      vector_streams[2])
+  device = scal_indices.device
+  scal_deq = _scalar.dequantize_assignments(scal_indices, scal_codebooks)
+  vec_deq = vector_dequantize(vec_indices, vec_codebook, vec_max_codewords)
+  if vec_deq.shape[1] != len(vec):
+    raise ValueError('vec_codebook must be (kmax, %d)' % len(vec))
+  codes = torch.zeros((b, s), dtype=torch.float32, device=device)
+  codes.index_copy_(1, torch.tensor(scal, dtype=torch.int64, device=device),
+                    scal_deq)
+  codes.index_copy_(1, torch.tensor(vec, dtype=torch.int64, device=device),
+                    vec_deq)
+  return codes
+
+
 def _gathered(codes, cluster):
   codes = _scalar._codes(codes)
   cluster = _cluster(cluster, codes.shape[1], 'cluster')
@@ -595,13 +689,17 @@ def _mixed_point(who, training, source_code, from_stream, rows_per_stream,
                  huff_tab1, huff_tab2, *args, **kwargs):
   """compute_RD_point_mixed for Mod2 / Mod3: (rate, distortion, huff_tab1,
   huff_tab2), the two tables None under 'entropy'."""
-  _scalar._check_source_code(source_code)
-  _scalar._check_from_stream(from_stream, source_code)
-  if source_code not in _scalar._TABLE_CODES:
+  _check_mixed_source_code(source_code, from_stream)
+  if source_code not in _scalar._TABLE_CODES + (_SPLIT_CODE,):
     return compute_RD_point_mixed(*args, **kwargs) + (None, None)
   tables = None
   if not training:
-    _scalar._need_tables(who, huff_tab1, huff_tab2, source_code=source_code)
+    if source_code != _SPLIT_CODE:
+      _scalar._need_tables(who, huff_tab1, huff_tab2, source_code=source_code)
+    elif huff_tab1 is None or huff_tab2 is None:
+      raise ValueError("%s: source_code='ans_split' with precomputed "
+                       'codebooks needs the frequencies of the training call '
+                       'as well' % who)
     tables = (huff_tab1, huff_tab2)
   rate, distortion, tables = compute_RD_point_mixed(
       *args, source_code=source_code, tables=tables, from_stream=from_stream,
@@ -657,7 +755,9 @@ def Mod2_compute_RD_point(codes, patches, dictionary, scal_clusts, vec_clust,
   source_code 'huffman' and 'ans' code at most 4096 symbols, so a training
   call under them cuts a larger fit down with trim_vector_codebook first and
   raises NotImplementedError only if more than 4096 codewords are still in
-  use."""
+  use.  source_code='ans_split' (compute_RD_point_mixed) codes the vector
+  index with up to 131072 symbols: nothing is cut down, huff_tab1 is the
+  scalar frequency array and huff_tab2 the pair (freq_hi, freq_lo)."""
   training = precomputed_scal_codebook is None
   if training:
     scal_cbook = _scalar._uniform_for(_gathered(codes, scal_clusts),

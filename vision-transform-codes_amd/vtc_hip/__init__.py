@@ -359,6 +359,28 @@ VQ_LARGE_SIGNATURES = {
     'vtc_vq_large_index_counts': (_i32, [_vp, _i64, _i32, _vp, _vp]),
 }
 
+INDEX_ANS_SPLIT_ABI_VERSION = 1   # VTC_INDEX_ANS_SPLIT_ABI_VERSION
+INDEX_ANS_SPLIT_MAX_SYMBOLS = 131072   # VTC_INDEX_ANS_SPLIT_MAX_SYMBOLS
+INDEX_ANS_SPLIT_LO_BITS = 8            # VTC_INDEX_ANS_SPLIT_LO_BITS
+
+# The thirteenth header, include/ext/vtc_index_ans_split.h (same library): the
+# range coder of the eleventh for one index column of up to 131 072 symbols,
+# every index split into two symbols.  Again a table of its own.  The header
+# extends the eleventh and sits under include/ext/, and the table is named
+# ..._BINDINGS: the twelve ..._SIGNATURES tables stay the twelve headers
+# directly under include/, a set that tests/test_vq_large_host.py counts.
+INDEX_ANS_SPLIT_BINDINGS = {
+    'vtc_index_ans_split_abi_version': (_i32, []),
+    'vtc_index_ans_split_workspace_bytes': (_sz, [_i32]),
+    'vtc_index_ans_split_sizes': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp,
+                                         _vp, _vp, _sz, _vp]),
+    'vtc_index_ans_split_pack': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp,
+                                        _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    'vtc_index_ans_split_unpack': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp,
+                                          _i32, _i32, _vp, _vp, _vp, _vp, _sz,
+                                          _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -379,7 +401,7 @@ def load_library():
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
                 QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
                 INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES,
-                VQ_LARGE_SIGNATURES):
+                VQ_LARGE_SIGNATURES, INDEX_ANS_SPLIT_BINDINGS):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -409,6 +431,8 @@ def load_library():
   if lib.vtc_vq_large_abi_version() != VQ_LARGE_ABI_VERSION:
     raise ImportError('libvtc_hip.so large vector quantiser ABI version '
                       'mismatch')
+  if lib.vtc_index_ans_split_abi_version() != INDEX_ANS_SPLIT_ABI_VERSION:
+    raise ImportError('libvtc_hip.so split index ANS ABI version mismatch')
   _lib = lib
   return lib
 
