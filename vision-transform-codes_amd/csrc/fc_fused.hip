@@ -686,9 +686,23 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
 // conflict.  The 8-byte publishing stores go out in groups of 16 consecutive
 // lanes = 16 rows of one half at 2-bank slots 2 * row (+ 2 for the swap)
 // mod 16: 2-way, as the 32x32x16 kernel's stores are.
-template <int NPH, int NP, int MODE, bool F16 = false, bool STAMP = false>
+//
+// SCHED moves VALU work between stream segments; arithmetic, bytes and
+// products are the same in every schedule, and so are the codes, bit for bit
+// (profiles/fused_epilogue_spread.txt).
+//   bit 0: the epilogue of a middle phase p (0 < p < NPH-1) runs half under
+//          step 3(p-1) (groups 0, 1) and half under step 1(p+1) (groups 2, 3)
+//          instead of wholly under step 1(p+1).  NPH = 2 has no middle phase.
+//   bit 1: the iteration's last step 3 walks its fragments pixel-block-major
+//          (blocks {0, 1} over the four k-steps, then {2, 3}), and the residual
+//          exchange of blocks 0 and 1 runs in the MFMA gaps of the second half.
+template <int NPH, int NP, int MODE, bool F16 = false, bool STAMP = false,
+          int SCHED = 0>
 __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   static_assert(!F16 || NP == 2, "the f16 split exists as three products only");
+  static_assert(SCHED >= 0 && SCHED < 4, "two schedule bits");
+  constexpr bool SPREAD = (SCHED & 1) != 0 && NPH > 2;
+  constexpr bool EARLY_R = (SCHED & 2) != 0;
   using L = FusedLds<NPH, NP>;
   constexpr int CREG = L::CREG;
   constexpr int CR = CREG > 0 ? CREG : 1;
@@ -899,9 +913,16 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   ((sg) == 0 ? 0                                                 \
              : (sg) == 2 * NPH - 1 ? NPH - 1                     \
                                    : ((sg) % 2 ? ((sg) + 1) / 2 : (sg) / 2 - 1))
-  // position i of a T segment: k-step i >> 2, pixel block i & 3
+  // position i of a T segment: k-step i >> 2, pixel block i & 3 -- except, with
+  // EARLY_R, in the iteration's last segment, which is walked block-major:
+  // k-step (i >> 1) & 3, pixel block 2 (i >> 3) + (i & 1)
+#define VTC_SEG_BLOCK_MAJOR(sg) (EARLY_R && (sg) == 2 * NPH - 1)
+#define VTC_T_NB(sg, i) \
+  (VTC_SEG_BLOCK_MAJOR(sg) ? 2 * ((i) >> 3) + ((i) & 1) : (i) & 3)
+#define VTC_T_KS(sg, i) (VTC_SEG_BLOCK_MAJOR(sg) ? ((i) >> 1) & 3 : (i) >> 2)
 #define VTC_LOAD_SEG(part, sg, i)                                          \
-  (VTC_SEG_IS_T(sg) ? VTC_LOAD_T(part, VTC_SEG_PHASE(sg), (i) & 3, (i) >> 2) \
+  (VTC_SEG_IS_T(sg) ? VTC_LOAD_T(part, VTC_SEG_PHASE(sg), VTC_T_NB(sg, i), \
+                                 VTC_T_KS(sg, i))                          \
                     : VTC_LOAD_A(part, VTC_SEG_PHASE(sg), (i)))
 #define VTC_REFILL(sg, i)                                                   \
   {                                                                         \
@@ -1049,6 +1070,151 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
     __syncthreads();
   };
 
+  // EARLY_R: exchange_r in pieces, the same operations on the same values.
+  // The guard factor depends on the previous call's Stat row only, so it is
+  // known before any block; a block is published as soon as its accumulators
+  // are final (times the factor: times 1 where exchange_r skips the product);
+  // the rescaling of the state and this call's maxima wait for the last block.
+  float xf[2] = {1.f, 1.f}, xm[2] = {0.f, 0.f};
+  auto exchange_guard = [&]() {
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      xf[n] = 1.f;
+      xm[n] = 0.f;
+      if (F16 && xr_calls > 0) {
+        const int row = 16 * n + c;
+        const float* prev = Stat + ((xr_calls - 1) & 1) * 128;
+        const float Mx = fmaxf(fmaxf(prev[row], prev[32 + row]),
+                               fmaxf(prev[64 + row], prev[96 + row]));
+        if (Mx > 2048.f && Mx < __builtin_inff())
+          xf[n] = ldexpf(1.f, 9 - ilogbf(Mx));
+      }
+    }
+  };
+  // in two stages, for one (block, patch half) under two positions: a the
+  // values (xv), b their parts into LDS
+  float xv[4];
+  auto exchange_block_a = [&](int nb, int n) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      xv[k] = sub_rn(Racc[nb][n][k], Xr[nb][n][k]);
+      if (F16) {
+        xv[k] *= r_scale;
+        xm[n] = fmaxf(xm[n], fabsf(xv[k]));
+        xv[k] *= xf[n];
+      }
+      Racc[nb][n][k] = 0.f;
+    }
+  };
+  auto exchange_block_b = [&](int nb, int n) {
+    uint2 hi, lo;
+    split_packed<F16, 4, NP == 2>(xv, hi, lo);
+    char* dst = Rx + rx_wr + 32 * nb + kRxHalf * n;
+    *reinterpret_cast<uint2*>(dst) = hi;
+    if (NP == 2) *reinterpret_cast<uint2*>(dst + kRxPart) = lo;
+  };
+  auto exchange_block = [&](int nb, int n) {
+    exchange_block_a(nb, n);
+    exchange_block_b(nb, n);
+  };
+  // blocks nb0.. (the ones no MFMA gap took), then the state
+  auto exchange_finish = [&](int nb0) {
+#pragma unroll
+    for (int nb = nb0; nb < 4; ++nb)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) exchange_block(nb, n);
+    if (F16) {
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        float m = xm[n];
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        if (q == 0) Stat[(xr_calls & 1) * 128 + w * 32 + 16 * n + c] = m * xf[n];
+      }
+      ++xr_calls;
+      if (__any(xf[0] != 1.f || xf[1] != 1.f)) {
+#pragma unroll
+        for (int p = 0; p < NPH; ++p)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) Y[p][e] *= xf[(e >> 2) & 1];
+#pragma unroll
+        for (int p = 0; p < CR; ++p)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) Cr[p][e] *= xf[(e >> 2) & 1];
+#pragma unroll
+        for (int pl = 0; pl < L::CL; ++pl)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            float4* c4 = reinterpret_cast<float4*>(Cst + cst_ln + pl * 16384 +
+                                                   g * 1024);
+            float4 cc = *c4;
+            const float fg = xf[g & 1];
+            cc.x *= fg; cc.y *= fg; cc.z *= fg; cc.w *= fg;
+            *c4 = cc;
+          }
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+#pragma unroll
+          for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) Xr[nb][n][k] *= xf[n];
+          cutoff_l[n] *= xf[n];
+          inv_sigma_y[n] *= 1.f / xf[n];
+        }
+      }
+    }
+    __syncthreads();
+  };
+
+  // EARLY_R: the iteration's last step 3, block-major: position i is k-step
+  // (i >> 1) & 3 of pixel block 2 (i >> 3) + (i & 1), so that blocks 0 and 1
+  // are final after position 7 (each accumulator still sums its k-steps in
+  // ascending order) and their exchange rides on positions 8..15.  The B
+  // operands are read twice, one patch half under each position of a k-step.
+  auto step3_last = [&](int buf, int sg) {
+    uint4 yb[2][NP], yb_next[2][NP];
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int part = 0; part < NP; ++part)
+        yb_next[n][part] = *reinterpret_cast<const uint4*>(
+            Yx + (buf * NP + part) * kYxPart + yx_rd + kYxHalf * n);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int j = i & 1, nb = VTC_T_NB(sg, i);
+      if (j == 0) {
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int part = 0; part < NP; ++part) yb[n][part] = yb_next[n][part];
+      }
+      if (i + 2 < 16) {
+#pragma unroll
+        for (int part = 0; part < NP; ++part)
+          yb_next[j][part] = *reinterpret_cast<const uint4*>(
+              Yx + (buf * NP + part) * kYxPart + yx_rd + kYxHalf * j +
+              64 * VTC_T_KS(sg, i + 2));
+      }
+      uint4 a[NP];
+#pragma unroll
+      for (int part = 0; part < NP; ++part) a[part] = ring[part][i % RING];
+      VTC_MFMA_PAIR(Racc[nb][0], Racc[nb][1], a, yb)
+      if (i == 6) {
+        exchange_guard();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (i >= 8) {
+        if (j == 0)
+          exchange_block_a((i - 8) >> 2, ((i - 8) >> 1) & 1);
+        else
+          exchange_block_b((i - 8) >> 2, ((i - 8) >> 1) & 1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      VTC_REFILL(sg, i)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
   // ---- R_0 = Y_0 D - X ---------------------------------------------------
   if (warm) {
 #pragma unroll
@@ -1130,11 +1296,68 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
       publish_group(Y[p], g, p & 1);
     }
   };
+  // SPREAD: epilogue_elem in two stages, the same operations on the same
+  // values, for one element under two positions: a position then carries about
+  // seven VALU instructions, which fit the issue gaps its MFMAs leave.
+  // a: the proximal step (cn4[k]); b: extrapolation, C and the publication.
+  auto epilogue_stage_a = [&](int p, int e, const f32x4 (&Gp)[4]) {
+    const int g = e >> 2, k = e & 3;
+    if (MODE == 7) {
+      cn4[k] = Y[p][e] + Gp[g][k];
+      return;
+    }
+    if (k == 0) {
+      if (p < CREG) {
+        cold4 = make_float4(Cr[p < CREG ? p : 0][4 * g + 0],
+                            Cr[p < CREG ? p : 0][4 * g + 1],
+                            Cr[p < CREG ? p : 0][4 * g + 2],
+                            Cr[p < CREG ? p : 0][4 * g + 3]);
+      } else {
+        cold4 = *reinterpret_cast<const float4*>(
+            Cst + cst_ln + (p - CREG) * 16384 + g * 1024);
+      }
+    }
+    const float cv = sub_rn(Y[p][e], mul_rn(eta, Gp[g][k]));
+    cn4[k] = shrink_fast<MODE>(cv, cutoff_l[g & 1]);
+  };
+  auto epilogue_stage_b = [&](int p, int e, float beta) {
+    const int g = e >> 2, k = e & 3;
+    const float cn = cn4[k];
+    if (MODE == 7) {
+      Y[p][e] = cn;
+    } else {
+      const float co = (k == 0) ? cold4.x : (k == 1) ? cold4.y
+                     : (k == 2) ? cold4.z : cold4.w;
+      Y[p][e] = fista ? add_rn(cn, mul_rn(beta, sub_rn(cn, co))) : cn;
+    }
+    if (k == 3) {
+      if (p < CREG) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Cr[p < CREG ? p : 0][4 * g + j] = cn4[j];
+      } else {
+        *reinterpret_cast<float4*>(Cst + cst_ln + (p - CREG) * 16384 +
+                                   g * 1024) =
+            make_float4(cn4[0], cn4[1], cn4[2], cn4[3]);
+      }
+      if (MODE != 7) publish_group(Y[p], g, p & 1);
+    }
+  };
+  // position i of a segment that carries half an epilogue: element
+  // e0 + (i >> 1), stage a under the even position, stage b under the odd one
+  auto epilogue_half = [&](int p, int e0, int i, const f32x4 (&Gp)[4],
+                           float beta) {
+    if ((i & 1) == 0)
+      epilogue_stage_a(p, e0 + (i >> 1), Gp);
+    else
+      epilogue_stage_b(p, e0 + (i >> 1), beta);
+  };
 
   // step 1 of phase p (stream segment sg): Gb[p&1] = D[tile] R_k; position
   // i = 2 ks + m.  The B operands of k-step ks + 1 are fetched under the two
-  // positions of k-step ks, one patch half each.
-  auto step1 = [&](int p, int sg, bool overlap, float beta) {
+  // positions of k-step ks, one patch half each.  overlap: 0 nothing, 1 the
+  // epilogue of phase p - 1, 2 (SPREAD) its groups 2 and 3, half an element
+  // under every position.
+  auto step1 = [&](int p, int sg, int overlap, float beta) {
     f32x4 (&G)[4] = Gb[p & 1];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -1166,8 +1389,11 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
 #pragma unroll
       for (int part = 0; part < NP; ++part) a[part] = ring[part][i % RING];
       VTC_MFMA_PAIR(G[2 * m], G[2 * m + 1], a, rb)
-      if (overlap) {
+      if (overlap == 1) {
         epilogue_elem(p - 1, i, Gb[(p - 1) & 1], beta);
+        __builtin_amdgcn_sched_barrier(0);
+      } else if (overlap == 2) {
+        epilogue_half(p - 1, 8, i, Gb[(p - 1) & 1], beta);
         __builtin_amdgcn_sched_barrier(0);
       }
       VTC_REFILL(sg, i)
@@ -1177,12 +1403,14 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
 
   for (int it = 0; it < P.num_iters; ++it) {
     const float beta = fista ? P.betas[it] : 0.f;
-    step1(0, 0, false, beta);
+    step1(0, 0, 0, beta);
     VTC_STAMP(0)
 #pragma unroll
     for (int p = 0; p < NPH; ++p) {
       if (p + 1 < NPH) {
-        step1(p + 1, 2 * p + 1, true, beta);   // + epilogue of phase p
+        // + epilogue of phase p; SPREAD: of a middle phase the half that
+        // step 3(p - 1) left
+        step1(p + 1, 2 * p + 1, (SPREAD && p > 0) ? 2 : 1, beta);
         VTC_STAMP(0)
       }
       __syncthreads();
@@ -1192,12 +1420,25 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
           epilogue_elem(NPH - 1, i, Gb[(NPH - 1) & 1], beta);
           __builtin_amdgcn_sched_barrier(0);
         });
+      } else if (SPREAD && p + 2 < NPH) {
+        // groups 0 and 1 of the middle phase p + 1: G(p + 1) is complete, and
+        // the barrier above put the last readers of exchange buffer (p + 1) & 1
+        // (step 3(p - 1)) behind us
+        step3(p, p & 1, true, 2 * p + 2, [&](int i) {
+          epilogue_half(p + 1, 0, i, Gb[(p + 1) & 1], beta);
+          __builtin_amdgcn_sched_barrier(0);
+        });
+      } else if (EARLY_R && p + 1 == NPH) {
+        step3_last(p & 1, 2 * NPH - 1);
       } else {
         step3(p, p & 1, true, (p + 1 < NPH) ? 2 * p + 2 : 2 * NPH - 1, nothing);
       }
       VTC_STAMP(3)
     }
-    exchange_r();
+    if (EARLY_R)
+      exchange_finish(2);
+    else
+      exchange_r();
     VTC_STAMP(4)
   }
   if (STAMP && lane == 0) {
@@ -1240,6 +1481,9 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
 #undef VTC_MFMA_PAIR
 #undef VTC_SEG_IS_T
 #undef VTC_SEG_PHASE
+#undef VTC_SEG_BLOCK_MAJOR
+#undef VTC_T_NB
+#undef VTC_T_KS
 }
 
 }  // namespace vtc
@@ -1298,18 +1542,40 @@ static bool use_tile16(int precision) {
   return default_tile16(precision);
 }
 
-template <int NPH, int NP, int MODE, bool F16, bool STAMP, bool TILE16>
+// Which schedule the 16x16x32 kernel runs by default: the spread epilogue for
+// f16x3 and bf16 (0.9 % and 2.8 % faster per step at the benchmark shape);
+// the early exchange is no gain and stays off, bf16x3 on this tile is a forced
+// arm and was not measured (profiles/fused_epilogue_spread.txt).
+template <int NP, bool F16>
+constexpr int default_sched() {
+  return (F16 || NP == 1) ? 1 : 0;
+}
+// VTC_FUSED_SCHED=0|1|2|3 forces a schedule: bit 0 spreads the epilogue of the
+// middle phases, bit 1 starts the residual exchange under the iteration's last
+// step 3 (a diagnostic switch, read on every call, as VTC_FUSED_TILE is).  The
+// 32x32x16 kernel has one schedule.
+static int use_sched(int by_default) {
+  const char* v = getenv("VTC_FUSED_SCHED");
+  if (v && v[0] >= '0' && v[0] <= '3' && v[1] == 0) return v[0] - '0';
+  return by_default;
+}
+
+template <int NPH, int NP, int MODE, bool F16, bool STAMP, bool TILE16,
+          int SCHED>
 static auto fused_kernel() {
-  if constexpr (TILE16)
+  static_assert(TILE16 || SCHED == 0, "schedules exist on the 16x16x32 tile");
+  if constexpr (TILE16 && SCHED != 0)
+    return fused_fista_kernel16<NPH, NP, MODE, F16, STAMP, SCHED>;
+  else if constexpr (TILE16)
     return fused_fista_kernel16<NPH, NP, MODE, F16, STAMP>;
   else
     return fused_fista_kernel<NPH, NP, MODE, F16, STAMP>;
 }
 
-template <int NPH, int NP, int MODE, bool F16, bool TILE16>
+template <int NPH, int NP, int MODE, bool F16, bool TILE16, int SCHED>
 static int launch_fused(const FusedParams& P, hipStream_t st) {
   using L = FusedLds<NPH, NP>;
-  auto kernel = fused_kernel<NPH, NP, MODE, F16, false, TILE16>();
+  auto kernel = fused_kernel<NPH, NP, MODE, F16, false, TILE16, SCHED>();
   static unsigned long long configured = 0;
   if (first_use_on_this_device(&configured)) {
     VTC_HIP_CHECK(hipFuncSetAttribute(
@@ -1325,13 +1591,14 @@ static int launch_fused(const FusedParams& P, hipStream_t st) {
 // Diagnostic: VTC_FUSED_STAMPS=1 runs the stamped instantiation (soft
 // threshold only) and prints per-segment cycle shares.  Its run time is not
 // representative (the stamps fence the schedule); read the shares only.
-template <int NPH, int NP, bool F16, bool TILE16>
+template <int NPH, int NP, bool F16, bool TILE16, int SCHED>
 static int launch_stamped(FusedParams P, hipStream_t st) {
   using L = FusedLds<NPH, NP>;
   static const bool no_epilogue = getenv("VTC_FUSED_NOEPI") != nullptr;
-  auto kernel = no_epilogue
-                    ? fused_kernel<NPH, NP, 7, F16, true, TILE16>()
-                    : fused_kernel<NPH, NP, VTC_SOFT, F16, true, TILE16>();
+  auto kernel =
+      no_epilogue
+          ? fused_kernel<NPH, NP, 7, F16, true, TILE16, SCHED>()
+          : fused_kernel<NPH, NP, VTC_SOFT, F16, true, TILE16, SCHED>();
   unsigned long long* dev = nullptr;
   VTC_HIP_CHECK(hipMalloc(&dev, 8 * sizeof(unsigned long long)));
   VTC_HIP_CHECK(hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), st));
@@ -1358,27 +1625,53 @@ static int launch_stamped(FusedParams P, hipStream_t st) {
   return VTC_OK;
 }
 
-template <int NPH, int NP, bool F16, bool TILE16>
+template <int NPH, int NP, bool F16, bool TILE16, int SCHED>
 static int dispatch_mode(const FusedParams& P, int threshold, hipStream_t st) {
   static const bool stamps = getenv("VTC_FUSED_STAMPS") != nullptr;
-  if (stamps && threshold == VTC_SOFT && NPH == 8 && NP == 2)
-    return launch_stamped<NPH, NP, F16, TILE16>(P, st);
-  switch (threshold) {
-    case VTC_SOFT: return launch_fused<NPH, NP, VTC_SOFT, F16, TILE16>(P, st);
-    case VTC_SOFT_NONNEG:
-      return launch_fused<NPH, NP, VTC_SOFT_NONNEG, F16, TILE16>(P, st);
-    case VTC_HARD: return launch_fused<NPH, NP, VTC_HARD, F16, TILE16>(P, st);
-    default: return launch_fused<NPH, NP, VTC_HARD_NONNEG, F16, TILE16>(P, st);
+  // the stamped run is of the benchmark's shape; schedule 0 keeps the
+  // instantiations it always had
+  if constexpr (SCHED == 0 || (NPH == 8 && NP == 2)) {
+    if (stamps && threshold == VTC_SOFT && NPH == 8 && NP == 2)
+      return launch_stamped<NPH, NP, F16, TILE16, SCHED>(P, st);
   }
+  switch (threshold) {
+    case VTC_SOFT:
+      return launch_fused<NPH, NP, VTC_SOFT, F16, TILE16, SCHED>(P, st);
+    case VTC_SOFT_NONNEG:
+      return launch_fused<NPH, NP, VTC_SOFT_NONNEG, F16, TILE16, SCHED>(P, st);
+    case VTC_HARD:
+      return launch_fused<NPH, NP, VTC_HARD, F16, TILE16, SCHED>(P, st);
+    default:
+      return launch_fused<NPH, NP, VTC_HARD_NONNEG, F16, TILE16, SCHED>(P, st);
+  }
+}
+
+// The schedule of a call: one on the 32x32x16 tile; on the other the switch's
+// or the default, without bit 0 where there is no middle phase (NPH = 2).
+template <int NPH, int NP, bool F16, bool TILE16>
+static int dispatch_sched(const FusedParams& P, int threshold,
+                          hipStream_t st) {
+  if constexpr (TILE16) {
+    const int sched = use_sched(default_sched<NP, F16>());
+    if constexpr (NPH > 2) {
+      if (sched == 1)
+        return dispatch_mode<NPH, NP, F16, TILE16, 1>(P, threshold, st);
+      if (sched == 3)
+        return dispatch_mode<NPH, NP, F16, TILE16, 3>(P, threshold, st);
+    }
+    if (sched & 2)
+      return dispatch_mode<NPH, NP, F16, TILE16, 2>(P, threshold, st);
+  }
+  return dispatch_mode<NPH, NP, F16, TILE16, 0>(P, threshold, st);
 }
 
 template <int NP, bool F16, bool TILE16>
 static int dispatch_phases(const FusedParams& P, int threshold,
                            hipStream_t st) {
   switch (phases_for(P.s)) {
-    case 2: return dispatch_mode<2, NP, F16, TILE16>(P, threshold, st);
-    case 4: return dispatch_mode<4, NP, F16, TILE16>(P, threshold, st);
-    case 8: return dispatch_mode<8, NP, F16, TILE16>(P, threshold, st);
+    case 2: return dispatch_sched<2, NP, F16, TILE16>(P, threshold, st);
+    case 4: return dispatch_sched<4, NP, F16, TILE16>(P, threshold, st);
+    case 8: return dispatch_sched<8, NP, F16, TILE16>(P, threshold, st);
   }
   set_error("fused FISTA: unsupported atom count %d", P.s);
   return VTC_ERR_UNSUPPORTED;
