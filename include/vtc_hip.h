@@ -268,7 +268,15 @@ int vtc_conv_ista_fista(const float* images_padded, const float* dictionary,
 
 /* ---- dictionary update, fully-connected (rows a5, a6, a7) --------------- */
 size_t vtc_fc_dict_gradient_workspace_bytes(int64_t b, int64_t n, int64_t s);
-/* grad_sum (s,n) = codes^T (codes dictionary - images): NOT divided by b. */
+/* grad_sum (s,n) = codes^T (codes dictionary - images): NOT divided by b.
+ * Precision: float32 level on every route, bitwise reproducible from run to
+ * run.  Batches of 1024 rows and more with 16-byte aligned pointers and n, s
+ * multiples of 64 run both contractions on the 16-bit matrix pipe with every
+ * float32 value split exactly into three bf16 parts and the six largest part
+ * products kept (truncation below 2^-24 of a product); everything else runs
+ * the exact-f32 matrix instructions.  The two routes differ in the last bits
+ * only (order of accumulation).  VTC_FC_GRAD=f32|b3 in the environment forces
+ * a route where its preconditions hold (a diagnostic switch). */
 int vtc_fc_dict_gradient(const float* images, const float* dictionary,
                          const float* codes, float* grad_sum, int64_t b,
                          int64_t n, int64_t s, void* workspace,

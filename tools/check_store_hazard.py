@@ -22,7 +22,7 @@ WIDE = re.compile(r'^\s*buffer_store_dwordx[34]\s+v\[\d+:\d+\],\s*([^,]+),\s*'
                   r's\[\d+:\d+\],\s*(\S+)')
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-ffp-contract=off',
          '--cuda-device-only', '-S', '-I', str(REPO / 'include')]
-NO_SLP = {'fc_fused.hip', 'conv.hip'}
+NO_SLP = {'fc_fused.hip', 'conv.hip', 'fc_gradient_b3.hip'}
 
 
 def main():

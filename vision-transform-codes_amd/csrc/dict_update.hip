@@ -9,13 +9,21 @@
 //
 // The update is split in two calls so that a data-parallel caller can
 // all-reduce the un-normalised gradient sum between them:
-//   gradient : G = C^T (C D - X)             two exact-f32 MFMA contractions,
-//                                            the second split over the batch
-//                                            (K = b) into slabs summed in a
-//                                            fixed order -> reproducible
+//   gradient : G = C^T (C D - X)             two contractions, the second
+//                                            split over the batch (K = b) into
+//                                            slabs summed in a fixed order ->
+//                                            reproducible.  Exact-f32 MFMA
+//                                            (gemm_f32.h) or, for large
+//                                            aligned batches, the exact
+//                                            three-part bf16 split on the
+//                                            16-bit matrix pipe (gemm_b3.h)
 //   apply    : D -= eta_d * (G / b) [/ (h + 1e-3)] ; D /= ||row||
 #include "common.h"
+#include "gemm_b3.h"
 #include "gemm_f32.h"
+
+#include <stdlib.h>
+#include <string.h>
 
 namespace vtc {
 
@@ -347,6 +355,23 @@ extern "C" int vtc_gram(const float* a, int64_t rows, int64_t cols,
                                      st);
 }
 
+// Which contraction the gradient runs on.  The three-part bf16 route (b3)
+// where its preconditions hold (fc_gradient_b3_usable) and the batch is past
+// the measured cut-over (fc_gradient_b3_faster); VTC_FC_GRAD=f32|b3 forces a
+// route (a diagnostic switch, read on every call so that one process can run
+// both; b3x1: the b3 route with all six products in one accumulator set,
+// which measures 1.8e-7 from float64 where two sets measure 7e-8).  A forced
+// b3 whose preconditions fail runs f32.
+enum FcGradRoute { kFcGradF32, kFcGradB3, kFcGradB3OneSet };
+static FcGradRoute fc_gradient_route(bool usable, bool faster) {
+  const char* v = getenv("VTC_FC_GRAD");
+  FcGradRoute want = faster ? kFcGradB3 : kFcGradF32;
+  if (v && !strcmp(v, "f32")) want = kFcGradF32;
+  if (v && !strcmp(v, "b3")) want = kFcGradB3;
+  if (v && !strcmp(v, "b3x1")) want = kFcGradB3OneSet;
+  return usable ? want : kFcGradF32;
+}
+
 extern "C" size_t vtc_fc_dict_gradient_workspace_bytes(int64_t b, int64_t n,
                                                        int64_t s) {
   if (b <= 0 || n <= 0 || s <= 0) return 256;
@@ -371,6 +396,16 @@ extern "C" int vtc_fc_dict_gradient(const float* images,
   Carver ws(workspace);
   const FcGradLayout L(ws, b, n, s);
   const int slices = gradient_slices(b, n, s);
+  const FcGradRoute route = fc_gradient_route(
+      fc_gradient_b3_usable(images, dictionary, codes, grad_sum, b, n, s,
+                            slices),
+      fc_gradient_b3_faster(b, n, s));
+  if (route != kFcGradF32) {
+    int rc = launch_fc_gradient_b3(images, dictionary, codes, L.E, L.slabs,
+                                   slices, b, n, s, route == kFcGradB3, st);
+    if (rc != VTC_OK) return rc;
+    return launch_slab_reduce(L.slabs, slices, s * n, grad_sum, st);
+  }
   // E = C D - X
   EpiMinus e1{L.E, images, n, n};
   int rc = launch_gemm_f32<true, false>(codes, s, dictionary, n, b, n, s, 1,

@@ -146,4 +146,26 @@ __device__ __forceinline__ void split_packed(
   split_packed_as<F16, W, LO, true>(v, scale, hi, lo);
 }
 
+// The exact three-part bf16 split (gemm_b3.h):
+//   h = bf16(x),  m = bf16(x - h),  l = bf16(x - h - m)   (nearest even)
+// 8 + 8 + 8 significand bits cover the 24 of a float32, both subtractions are
+// exact, so h + m + l == x; bf16 has the exponent range of f32, so operands
+// enter as they are.  Every part product is exact in f32.  A product keeps
+// hh, hm, mh, hl, lh and mm (6 MFMA); the dropped ml, lm and ll are below
+// 2^-24 of the product each.  W = 4 values -> packed parts.
+__device__ __forceinline__ void split3_packed(const float (&v)[4], uint2& h_out,
+                                              uint2& m_out, uint2& l_out) {
+  bf16x4 h, m, l;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    h[k] = (__bf16)v[k];
+    const float r1 = v[k] - (float)h[k];
+    m[k] = (__bf16)r1;
+    l[k] = (__bf16)(r1 - (float)m[k]);
+  }
+  h_out = __builtin_bit_cast(uint2, h);
+  m_out = __builtin_bit_cast(uint2, m);
+  l_out = __builtin_bit_cast(uint2, l);
+}
+
 }  // namespace vtc
