@@ -75,6 +75,21 @@ def get_jpeg_quant_hifi_binwidths():
   return matrix_zigzag.zigzag(table_k1)
 
 
+def get_jpeg_quant_chroma_binwidths():
+  """The chrominance quantisation table of ITU-T T.81 Annex K.2 (for data in
+  [0, 255]) in zig-zag order, float64 (64,): the bin widths of the Cb and Cr
+  planes of utils.color.rate_distortion_image_color."""
+  table_k2 = np.array([[17, 18, 24, 47, 99, 99, 99, 99],
+                       [18, 21, 26, 66, 99, 99, 99, 99],
+                       [24, 26, 56, 99, 99, 99, 99, 99],
+                       [47, 66, 99, 99, 99, 99, 99, 99],
+                       [99, 99, 99, 99, 99, 99, 99, 99],
+                       [99, 99, 99, 99, 99, 99, 99, 99],
+                       [99, 99, 99, 99, 99, 99, 99, 99],
+                       [99, 99, 99, 99, 99, 99, 99, 99]])
+  return matrix_zigzag.zigzag(table_k2)
+
+
 def compute_huffman_table(symb2freq):
   """{symbol: codeword} of the Huffman code of {symbol: weight}.
 

@@ -3,7 +3,8 @@ Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
 include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h,
 include/vtc_vq.h, include/vtc_index_code.h, include/vtc_index_decode.h and
-include/vtc_index_ans.h).
+include/vtc_index_ans.h; include/vtc_vq_large.h and the two headers under
+include/ext/ are named at their tables).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
 current HIP stream, torch.distributed -- and nothing else: every arithmetic
@@ -381,6 +382,25 @@ INDEX_ANS_SPLIT_BINDINGS = {
                                           _vp]),
 }
 
+COLOR_ABI_VERSION = 1   # VTC_COLOR_ABI_VERSION
+COLOR_HWC, COLOR_CHW = range(2)                 # VTC_COLOR_HWC, VTC_COLOR_CHW
+UPSAMPLE_REPLICATE, UPSAMPLE_TRIANGLE = range(2)   # VTC_UPSAMPLE_*
+
+# The fourteenth header, include/ext/vtc_color.h (same library): the colour
+# step of an image-level R-D point -- a 3 x 3 affine map per pixel, chroma
+# planes down to reduced resolution and back.  Under include/ext/ and named
+# ..._BINDINGS for the reason given above.  matrix, pre and post are HOST
+# pointers to doubles.
+COLOR_BINDINGS = {
+    'vtc_color_abi_version': (_i32, []),
+    'vtc_color_transform': (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _i32,
+                                   _vp, _vp, _vp, _i32, _f64, _f64, _vp]),
+    'vtc_plane_downsample': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32,
+                                    _vp]),
+    'vtc_plane_upsample': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32,
+                                  _i32, _i32, _i32, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -401,7 +421,8 @@ def load_library():
                 DECODE_SIGNATURES, QUALITY_SIGNATURES, STATS_SIGNATURES,
                 QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
                 INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES,
-                VQ_LARGE_SIGNATURES, INDEX_ANS_SPLIT_BINDINGS):
+                VQ_LARGE_SIGNATURES, INDEX_ANS_SPLIT_BINDINGS,
+                COLOR_BINDINGS):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -433,6 +454,8 @@ def load_library():
                       'mismatch')
   if lib.vtc_index_ans_split_abi_version() != INDEX_ANS_SPLIT_ABI_VERSION:
     raise ImportError('libvtc_hip.so split index ANS ABI version mismatch')
+  if lib.vtc_color_abi_version() != COLOR_ABI_VERSION:
+    raise ImportError('libvtc_hip.so colour ABI version mismatch')
   _lib = lib
   return lib
 
