@@ -289,6 +289,7 @@ def _fft_pair(device, hold, entry, run, make_inputs):
     staged = {k: held_stream.poisoned_like(v, device) for k, v in dev.items()}
     jobs.append((s, staged, want))
   torch.cuda.synchronize(device)
+  window = time.perf_counter()
   for s, staged, _ in jobs:
     with torch.cuda.stream(s):
       hold.sleep()
@@ -302,13 +303,15 @@ def _fft_pair(device, hold, entry, run, make_inputs):
       got.append(run(lib, {k: v[0] for k, v in staged.items()},
                      ctypes.c_void_p(s.cuda_stream)))
     canaries.append(held_stream.canary(first))
+  window_ms = (time.perf_counter() - window) * 1e3
   sa.synchronize()
   sb.synchronize()
   torch.cuda.synchronize(device)
-  for word in canaries:
+  for index, word in enumerate(canaries):
     assert held_stream.is_poison(word), (
         '%s on two streams proved nothing: a stream was released before both '
-        'calls were enqueued' % entry)
+        'calls were enqueued (canary %d of 4; enqueued in %.3f ms on the host, '
+        'delay %.1f ms)' % (entry, index, window_ms, hold.delay_ms))
   for name, (_, _, want), out in zip('AB', jobs, got):
     assert bool(torch.isfinite(out).all()), (entry, name)
     assert torch.equal(out, want), (
