@@ -335,11 +335,6 @@ __device__ __forceinline__ float wave_maxf(float v) {
   }
   return v;
 }
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __device__ __forceinline__ bool pair_in_range(int i, int j, int max_column) {
   return i >= 0 && i < max_column && j >= 0 && j < max_column;

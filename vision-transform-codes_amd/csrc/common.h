@@ -172,6 +172,11 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
 // maximum of unsigned words: bit patterns of non-negative floats are ordered
 // like the floats, NaN on top
 __device__ __forceinline__ unsigned wave_max(unsigned v) {

@@ -2,14 +2,15 @@
 // (include/vtc_index_ans.h): stream sizes, the packed streams and the way back.
 // DESIGN.md 4.19 states the code; the header is the contract.
 //
-// A stream carries 64 interleaved states and position t belongs to state
-// t % 64, so ONE WAVE codes ONE STREAM whatever m is: in step q lane l holds
-// position 64 q + l, the step's 64 indices are consecutive in memory (one
-// coalesced access), and the words of a step go to consecutive places in lane
-// order (ballot + popcount of the lower lanes).  256-thread blocks, 4 streams.
+// The stream format and its coder (one wave codes one stream, the words of a
+// step in lane order) are stated in ans_stream.h.  This file states the model:
+// m columns with one frequency table each, position t of a stream under the
+// table of column t % m.  In step q lane l holds position 64 q + l, so the
+// step's 64 indices are consecutive in memory (one coalesced access) and a
+// lane's column moves by 64 % m per step.  256-thread blocks, 4 streams.
 //
 // Launches per call, all on the caller's stream:
-//   1. ans_begin_kernel: status and the workspace's bad-column flag
+//   1. ans_begin_kernel: status and the workspace's bad-column word
 //   2. ans_cum_kernel, one block per column: exclusive integer scan of the
 //      column's frequencies into the workspace, and the check of their sum
 //   3. ans_encode_kernel<stores> or ans_decode_kernel
@@ -26,36 +27,24 @@
 // (the symbol of every 128th slot, built by ans_cum_kernel) bounds it, and a
 // binary search over the column's `cum` finishes it, at most 12 probes and
 // none where one symbol covers the bucket.
-#include <limits.h>
-
-#include "../../include/vtc_index_ans.h"
-#include "common.h"
+#include "ans_stream.h"
 
 namespace vtc {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kMaxColumns = VTC_INDEX_CODE_MAX_COLUMNS;
 constexpr int kMaxSymbols = VTC_INDEX_CODE_MAX_SYMBOLS;
-constexpr int kProbBits = VTC_INDEX_ANS_PROB_BITS;
-constexpr unsigned kProbScale = 1u << kProbBits;
-constexpr unsigned kLower = 1u << 16;            // L
-constexpr int kHeaderBytes = 4 * VTC_INDEX_ANS_LANES;
-constexpr int64_t kMaxStreamSymbols = (int64_t)1 << VTC_INDEX_ANS_MAX_STREAM_BITS;
 constexpr int kBucketBits = VTC_INDEX_ANS_BUCKET_BITS;
 constexpr int kBuckets = 1 << kBucketBits;             // of a column's 2^15 slots
 constexpr int kBucketShift = kProbBits - kBucketBits;
-typedef unsigned long long u64;
-constexpr u64 kNoPosition = ~0ull;
 
-static_assert(VTC_INDEX_ANS_LANES == 64, "one wave codes one stream");
 static_assert(kBuckets == kBlock, "ans_cum_kernel: one thread per bucket");
 
 struct IndexAnsLayout {
   uint16_t* cum;   // [m * kmax] exclusive cumulative sums, column j from j * kmax
   uint16_t* first; // [m * kBuckets] the symbol of a bucket's first slot
-  int32_t* bad;    // [1] smallest bad column, INT_MAX when none
+  int32_t* bad;    // [1] 1 + the smallest bad column, INT_MAX when none
+  IndexAnsLayout() = default;
   IndexAnsLayout(Carver& c, int m, int kmax) {
     cum = c.take<uint16_t>((size_t)m * kmax);
     first = c.take<uint16_t>((size_t)m * kBuckets);
@@ -63,109 +52,22 @@ struct IndexAnsLayout {
   }
 };
 
-__global__ void ans_begin_kernel(IndexAnsLayout ws, u64* status) {
-  *ws.bad = INT_MAX;
-  status[0] = 0;
-  status[1] = kNoPosition;   // minimum of flat positions or streams
-  status[2] = 0;
-}
-
-__global__ void ans_end_kernel(IndexAnsLayout ws, u64* status) {
-  status[1] = status[1] == kNoPosition ? 0 : status[1] + 1;
-  const int bad = *ws.bad;
-  if (bad != INT_MAX) status[2] = (u64)bad + 1;
-}
-
 // ---- tables -------------------------------------------------------------------
-// The largest i in [lo, hi] with cum[i] <= slot, given cum[lo] <= slot; at most
-// ceil(log2(hi - lo + 1)) probes, none when lo == hi.
-__device__ __forceinline__ int symbol_of(const uint16_t* cum, int lo, int hi,
-                                         unsigned slot) {
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (cum[mid] <= slot)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
-}
-
-// Thread t owns the `per` consecutive symbols from t * per on; the 256 partial
-// sums are scanned in LDS (Hillis-Steele, 8 rounds).  All sums are 32-bit: at
-// most 4096 * 65535.  The stored uint16 is exact for a column that passes the
-// check (its sums are at most 2^15); a bad column's is never read.
-// Then thread g finds the symbol of slot g << kBucketShift, the decoder's way
-// in: the symbol of any slot of bucket g lies between first[g] and
-// first[g + 1], which for the large frequencies of a sparse model are equal.
+// The column's scan (scan_row); then thread g finds the symbol of slot
+// g << kBucketShift, the decoder's way in: the symbol of any slot of bucket g
+// lies between first[g] and first[g + 1], which for the large frequencies of a
+// sparse model are equal.
 __global__ __launch_bounds__(kBlock) void ans_cum_kernel(
     const uint16_t* __restrict__ freq, int kmax, IndexAnsLayout ws) {
   __shared__ unsigned part[2][kBlock];
   const int tid = threadIdx.x;
   const int column = blockIdx.x;
   const int base = column * kmax;   // < 4096 * 4096
-  const int per = (kmax + kBlock - 1) / kBlock;
-  const int from = tid * per;
-  const int to = from + per < kmax ? from + per : kmax;
-  unsigned own = 0;
-  for (int i = from; i < to; ++i) own += freq[base + i];
-  part[0][tid] = own;
-  __syncthreads();
-  int in = 0;
-  for (int off = 1; off < kBlock; off <<= 1) {
-    unsigned v = part[in][tid];
-    if (tid >= off) v += part[in][tid - off];
-    part[in ^ 1][tid] = v;
-    in ^= 1;
-    __syncthreads();
-  }
-  unsigned run = part[in][tid] - own;   // exclusive
-  for (int i = from; i < to; ++i) {
-    ws.cum[base + i] = (uint16_t)run;
-    run += freq[base + i];
-  }
-  if (tid == kBlock - 1 && part[in][tid] != kProbScale)
-    atomicMin(ws.bad, column);
+  const unsigned total = scan_row(freq + base, ws.cum + base, kmax, part);
+  if (tid == kBlock - 1 && total != kProbScale) atomicMin(ws.bad, column + 1);
   __syncthreads();   // the block's cum is in global memory
   ws.first[column * kBuckets + tid] = (uint16_t)symbol_of(
       ws.cum + base, 0, kmax - 1, (unsigned)tid << kBucketShift);
-}
-
-// ---- shared pieces --------------------------------------------------------------
-struct StreamSpan {
-  int64_t base;   // flat position of the stream's first symbol
-  int count;      // its symbols, 1 .. 2^24
-  int steps;      // ceil(count / 64)
-};
-
-__device__ __forceinline__ StreamSpan stream_span(int64_t s, int64_t b, int m,
-                                                  int rows) {
-  StreamSpan span;
-  const int64_t row0 = s * rows;
-  const int64_t left = b - row0;
-  const int64_t here = left < rows ? left : rows;
-  span.base = row0 * m;
-  span.count = (int)(here * m);   // <= rows * m <= 2^24
-  span.steps = (span.count + 63) >> 6;
-  return span;
-}
-
-__device__ __forceinline__ unsigned lower_lanes(u64 mask, int lane) {
-  return (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-__device__ __forceinline__ u64 wave_min_u64(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // ---- encoding -------------------------------------------------------------------
@@ -207,30 +109,18 @@ __global__ __launch_bounds__(kBlock) void ans_encode_kernel(
     if (!kStore && lane == 0) sizes_out[s] = 0;
     return;
   }
-  const StreamSpan span = stream_span(s, b, m, rows);
-
-  // pack: the slot, and the words the caller's size leaves room for
-  uint8_t* slot = nullptr;
-  int room = 0;       // words
-  bool strayed = false;
-  if (kStore) {
-    const int64_t from = offsets[s], to = offsets[s + 1];
-    const int64_t size = sizes_in[s];
-    const bool fits = size >= kHeaderBytes && (size & 1) == 0 && from >= 0 &&
-                      from <= packed_bytes - size && from + size <= to;
-    if (!fits) {
-      if (lane == 0) atomicAdd(&status[2], 1ull);
-      return;
-    }
-    slot = packed + from;
-    room = (int)((size - kHeaderBytes) >> 1);
-  }
+  const StreamSpan span = stream_span(s, b, rows, m);
+  EncodeSlot out = {nullptr, 0};
+  if (kStore && !open_pack_slot(out, s, sizes_in, offsets, packed,
+                                packed_bytes, lane, status))
+    return;
 
   const int back = 64 % m;   // a lane's column moves by this much per step
   int t = (span.steps - 1) * 64 + lane;
   int column = t % m;
   unsigned x = kLower;
-  int cursor = room;   // pack: words still free in front; sizes: counts down
+  int cursor = out.room;   // pack: words still free in front; sizes: counts down
+  bool strayed = false;
   int uncodable = 0;
   u64 first = kNoPosition;
 
@@ -247,57 +137,14 @@ __global__ __launch_bounds__(kBlock) void ans_encode_kernel(
       ++uncodable;
       first = (u64)(span.base + t_here);   // steps descend: the last
     }                                            // one kept is the smallest
-    const bool emit =
-        now.f != 0 && (u64)x >= ((u64)now.f << (kProbBits + 2));
-    const u64 mask = __ballot(emit);
-    cursor -= __popcll(mask);
-    if (emit) {
-      if (kStore) {
-        const int w = cursor + (int)lower_lanes(mask, lane);
-        if (w >= 0 && w < room) {
-          uint8_t* at = slot + kHeaderBytes + 2 * (int64_t)w;
-          at[0] = (uint8_t)x;
-          at[1] = (uint8_t)(x >> 8);
-        } else {
-          strayed = true;
-        }
-      }
-      x >>= 16;
-    }
-    if (now.f != 0) x = ((x / now.f) << kProbBits) + x % now.f + now.c;
+    encode_phase<kStore>(now.f, now.c, x, cursor, out.slot, out.room, lane,
+                         strayed);
   }
-
-  if (kStore) {
-    uint8_t* at = slot + 4 * lane;   // room >= 0: the header is inside the slot
-    at[0] = (uint8_t)x;
-    at[1] = (uint8_t)(x >> 8);
-    at[2] = (uint8_t)(x >> 16);
-    at[3] = (uint8_t)(x >> 24);
-    // words lost at the front, or a size larger than the coder's own
-    if (__ballot(strayed || cursor != 0) && lane == 0)
-      atomicAdd(&status[2], 1ull);
-  } else if (lane == 0) {
-    sizes_out[s] = kHeaderBytes - 2 * cursor;   // cursor = -words
-  }
-
-  const int count = wave_sum_int(uncodable);
-  if (count) {   // the whole wave
-    first = wave_min_u64(first);
-    if (lane == 0) {
-      atomicAdd(&status[0], (u64)count);
-      atomicMin(&status[1], first);
-    }
-  }
+  finish_encode<kStore>(x, cursor, strayed, uncodable, first, out.slot, s, lane,
+                        sizes_out, status);
 }
 
 // ---- decoding -------------------------------------------------------------------
-__device__ __forceinline__ unsigned load_le(const uint8_t* __restrict__ at,
-                                            int bytes) {
-  unsigned v = 0;
-  for (int i = 0; i < bytes; ++i) v |= (unsigned)at[i] << (8 * i);
-  return v;
-}
-
 __global__ __launch_bounds__(kBlock) void ans_decode_kernel(
     const uint8_t* __restrict__ packed, int64_t packed_bytes,
     const int64_t* __restrict__ offsets, int64_t b, int m,
@@ -307,28 +154,15 @@ __global__ __launch_bounds__(kBlock) void ans_decode_kernel(
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t s = (int64_t)blockIdx.x * kWavesPerBlock + wave;
   if (s >= streams) return;   // the whole wave
-  const StreamSpan span = stream_span(s, b, m, rows);
+  const StreamSpan span = stream_span(s, b, rows, m);
   const bool decoding = *ws.bad == INT_MAX;
-
-  const int64_t from = offsets[s], next = offsets[s + 1];
-  const int64_t stop = next < packed_bytes ? next : packed_bytes;
-  bool malformed = false;
-  bool alive = decoding;
-  int room = 0;   // words of the slot
-  if (decoding && (from < 0 || from > next || stop - from < kHeaderBytes)) {
-    malformed = true;
-    alive = false;
-  }
-  const uint8_t* slot = packed;
-  unsigned x = kLower;
-  const bool opened = alive;   // the header is inside the slot
-  if (opened) {
-    slot = packed + from;
-    // a slot holds at most 2^24 words that a stream can use
-    const int64_t words = (stop - from - kHeaderBytes) >> 1;
-    room = words < kMaxStreamSymbols ? (int)words : (int)kMaxStreamSymbols;
-    x = load_le(slot + 4 * lane, 4);
-  }
+  unsigned x;
+  // a slot holds at most 2^24 words that a stream can use
+  const DecodeSlot in = open_decode_slot(decoding, s, offsets, packed,
+                                         packed_bytes, kMaxStreamSymbols, lane,
+                                         x);
+  bool alive = in.opened;
+  bool malformed = decoding && !in.opened;
 
   const int ahead = 64 % m;
   int t = lane;
@@ -350,40 +184,35 @@ __global__ __launch_bounds__(kBlock) void ans_decode_kernel(
       x = f * (x >> kProbBits) + at - cum[symbol];       // < 2^32
       need = x < kLower;
     }
-    const u64 mask = __ballot(need);
-    const int taken = __popcll(mask);
-    if (alive && cursor + taken > room) {   // out of words: the whole wave
-      alive = false;
+    if (alive && !refill(need, x, cursor, in.slot, in.room, lane)) {
+      alive = false;   // out of words: the whole wave
       malformed = true;
       symbol = -1;
-    }
-    if (alive) {
-      if (need) {
-        const int w = cursor + (int)lower_lanes(mask, lane);   // < room
-        x = x << 16 | load_le(slot + kHeaderBytes + 2 * (int64_t)w, 2);
-      }
-      cursor += taken;
     }
     if (active) indices[span.base + t] = symbol;
     t += 64;
     column += ahead;
     if (column >= m) column -= m;
   }
-
-  // the free integrity check; a stream that ran dry is already counted
-  if (alive && __ballot(x != kLower)) malformed = true;
-  if (lane == 0) {
-    used_bytes[s] = opened ? kHeaderBytes + 2 * cursor : 0;
-    if (malformed) {
-      atomicAdd(&status[0], 1ull);
-      atomicMin(&status[1], (u64)s);
-    }
-  }
+  finish_decode(alive, malformed, x, in.opened, cursor, s, lane, used_bytes,
+                status);
 }
 
-// VTC_OK when the calls take the shape; sets the error text otherwise.
-int check_shape(const char* who, int64_t b, int32_t m, int32_t kmax,
-                int32_t rows, int64_t* streams) {
+// ---- host side ------------------------------------------------------------------
+// What an entry point needs for its launches.
+struct AnsCall {
+  IndexAnsLayout ws;
+  int64_t streams;
+  int blocks;
+  hipStream_t st;
+  u64* flags;
+};
+
+// The checks that the three calls share, in their order (shape, packed_bytes,
+// workspace), then the carve.  VTC_OK, or the error with its text set.
+int open_call(const char* who, int64_t b, int32_t m, int32_t kmax, int32_t rows,
+              int64_t packed_bytes, int64_t* status, void* workspace,
+              size_t workspace_bytes, void* stream, AnsCall* call) {
   VTC_REQUIRE(b >= 1, "%s: bad size b = %lld", who, (long long)b);
   VTC_REQUIRE(m >= 1, "%s: bad size m = %d", who, m);
   VTC_REQUIRE(kmax >= 1, "%s: bad size kmax = %d", who, kmax);
@@ -401,22 +230,18 @@ int check_shape(const char* who, int64_t b, int32_t m, int32_t kmax,
               (long long)rows * m, (long long)kMaxStreamSymbols);
     return VTC_ERR_UNSUPPORTED;
   }
-  *streams = ceil_div(b, rows);
-  if (ceil_div(*streams, kWavesPerBlock) >= (int64_t)1 << 31) {
-    set_error("%s: b = %lld, too many streams", who, (long long)b);
-    return VTC_ERR_UNSUPPORTED;
-  }
-  return VTC_OK;
-}
-
-int check_workspace(const char* who, int32_t m, int32_t kmax,
-                    const void* workspace, size_t workspace_bytes) {
-  const size_t need = vtc_index_ans_workspace_bytes(m, kmax);
-  if (!workspace || workspace_bytes < need) {
-    set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
-              need);
-    return VTC_ERR_WORKSPACE;
-  }
+  int rc = check_streams(who, b, rows, &call->streams);
+  if (rc != VTC_OK) return rc;
+  VTC_REQUIRE(packed_bytes >= 0 && packed_bytes < (int64_t)1 << 59,
+              "%s: bad size packed_bytes = %lld", who, (long long)packed_bytes);
+  rc = check_workspace(who, vtc_index_ans_workspace_bytes(m, kmax), workspace,
+                       workspace_bytes);
+  if (rc != VTC_OK) return rc;
+  Carver carve(workspace);
+  call->ws = IndexAnsLayout(carve, m, kmax);
+  call->blocks = (int)ceil_div(call->streams, kWavesPerBlock);
+  call->st = as_stream(stream);
+  call->flags = reinterpret_cast<u64*>(status);
   return VTC_OK;
 }
 
@@ -443,22 +268,16 @@ extern "C" int vtc_index_ans_sizes(const int32_t* indices, int64_t b,
   const char* who = "vtc_index_ans_sizes";
   VTC_REQUIRE(indices && freq && stream_bytes && status, "%s: null pointer",
               who);
-  int64_t streams;
-  int rc = check_shape(who, b, m, kmax, rows_per_stream, &streams);
+  AnsCall c;   // no packed bytes: 0 passes their check
+  const int rc = open_call(who, b, m, kmax, rows_per_stream, 0, status,
+                           workspace, workspace_bytes, stream, &c);
   if (rc != VTC_OK) return rc;
-  rc = check_workspace(who, m, kmax, workspace, workspace_bytes);
-  if (rc != VTC_OK) return rc;
-  Carver carve(workspace);
-  const IndexAnsLayout ws(carve, m, kmax);
-  hipStream_t st = as_stream(stream);
-  u64* flags = reinterpret_cast<u64*>(status);
-  const int blocks = (int)ceil_div(streams, kWavesPerBlock);
-  ans_begin_kernel<<<1, 1, 0, st>>>(ws, flags);
-  ans_cum_kernel<<<m, kBlock, 0, st>>>(freq, kmax, ws);
-  ans_encode_kernel<false><<<blocks, kBlock, 0, st>>>(
-      indices, b, m, freq, kmax, rows_per_stream, streams, ws, stream_bytes,
-      nullptr, nullptr, nullptr, 0, flags);
-  ans_end_kernel<<<1, 1, 0, st>>>(ws, flags);
+  ans_begin_kernel<<<1, 1, 0, c.st>>>(c.ws.bad, c.flags);
+  ans_cum_kernel<<<m, kBlock, 0, c.st>>>(freq, kmax, c.ws);
+  ans_encode_kernel<false><<<c.blocks, kBlock, 0, c.st>>>(
+      indices, b, m, freq, kmax, rows_per_stream, c.streams, c.ws,
+      stream_bytes, nullptr, nullptr, nullptr, 0, c.flags);
+  ans_end_kernel<<<1, 1, 0, c.st>>>(c.ws.bad, c.flags);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }
@@ -474,26 +293,18 @@ extern "C" int vtc_index_ans_pack(const int32_t* indices, int64_t b, int32_t m,
   const char* who = "vtc_index_ans_pack";
   VTC_REQUIRE(indices && freq && stream_bytes && offsets && packed && status,
               "%s: null pointer", who);
-  int64_t streams;
-  int rc = check_shape(who, b, m, kmax, rows_per_stream, &streams);
+  AnsCall c;
+  const int rc = open_call(who, b, m, kmax, rows_per_stream, packed_bytes,
+                           status, workspace, workspace_bytes, stream, &c);
   if (rc != VTC_OK) return rc;
-  VTC_REQUIRE(packed_bytes >= 0 && packed_bytes < (int64_t)1 << 59,
-              "%s: bad size packed_bytes = %lld", who, (long long)packed_bytes);
-  rc = check_workspace(who, m, kmax, workspace, workspace_bytes);
-  if (rc != VTC_OK) return rc;
-  Carver carve(workspace);
-  const IndexAnsLayout ws(carve, m, kmax);
-  hipStream_t st = as_stream(stream);
-  u64* flags = reinterpret_cast<u64*>(status);
-  const int blocks = (int)ceil_div(streams, kWavesPerBlock);
   if (packed_bytes)
-    VTC_HIP_CHECK(hipMemsetAsync(packed, 0, (size_t)packed_bytes, st));
-  ans_begin_kernel<<<1, 1, 0, st>>>(ws, flags);
-  ans_cum_kernel<<<m, kBlock, 0, st>>>(freq, kmax, ws);
-  ans_encode_kernel<true><<<blocks, kBlock, 0, st>>>(
-      indices, b, m, freq, kmax, rows_per_stream, streams, ws, nullptr,
-      stream_bytes, offsets, packed, packed_bytes, flags);
-  ans_end_kernel<<<1, 1, 0, st>>>(ws, flags);
+    VTC_HIP_CHECK(hipMemsetAsync(packed, 0, (size_t)packed_bytes, c.st));
+  ans_begin_kernel<<<1, 1, 0, c.st>>>(c.ws.bad, c.flags);
+  ans_cum_kernel<<<m, kBlock, 0, c.st>>>(freq, kmax, c.ws);
+  ans_encode_kernel<true><<<c.blocks, kBlock, 0, c.st>>>(
+      indices, b, m, freq, kmax, rows_per_stream, c.streams, c.ws, nullptr,
+      stream_bytes, offsets, packed, packed_bytes, c.flags);
+  ans_end_kernel<<<1, 1, 0, c.st>>>(c.ws.bad, c.flags);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }
@@ -508,24 +319,16 @@ extern "C" int vtc_index_ans_unpack(const uint8_t* packed, int64_t packed_bytes,
   const char* who = "vtc_index_ans_unpack";
   VTC_REQUIRE(packed && offsets && freq && indices && used_bytes && status,
               "%s: null pointer", who);
-  int64_t streams;
-  int rc = check_shape(who, b, m, kmax, rows_per_stream, &streams);
+  AnsCall c;
+  const int rc = open_call(who, b, m, kmax, rows_per_stream, packed_bytes,
+                           status, workspace, workspace_bytes, stream, &c);
   if (rc != VTC_OK) return rc;
-  VTC_REQUIRE(packed_bytes >= 0 && packed_bytes < (int64_t)1 << 59,
-              "%s: bad size packed_bytes = %lld", who, (long long)packed_bytes);
-  rc = check_workspace(who, m, kmax, workspace, workspace_bytes);
-  if (rc != VTC_OK) return rc;
-  Carver carve(workspace);
-  const IndexAnsLayout ws(carve, m, kmax);
-  hipStream_t st = as_stream(stream);
-  u64* flags = reinterpret_cast<u64*>(status);
-  const int blocks = (int)ceil_div(streams, kWavesPerBlock);
-  ans_begin_kernel<<<1, 1, 0, st>>>(ws, flags);
-  ans_cum_kernel<<<m, kBlock, 0, st>>>(freq, kmax, ws);
-  ans_decode_kernel<<<blocks, kBlock, 0, st>>>(
+  ans_begin_kernel<<<1, 1, 0, c.st>>>(c.ws.bad, c.flags);
+  ans_cum_kernel<<<m, kBlock, 0, c.st>>>(freq, kmax, c.ws);
+  ans_decode_kernel<<<c.blocks, kBlock, 0, c.st>>>(
       packed, packed_bytes, offsets, b, m, freq, kmax, rows_per_stream,
-      streams, ws, indices, used_bytes, flags);
-  ans_end_kernel<<<1, 1, 0, st>>>(ws, flags);
+      c.streams, c.ws, indices, used_bytes, c.flags);
+  ans_end_kernel<<<1, 1, 0, c.st>>>(c.ws.bad, c.flags);
   VTC_LAUNCH_CHECK();
   return VTC_OK;
 }

@@ -35,11 +35,6 @@ constexpr int kEob = 0x00, kZrl = 0xF0;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kBlock * kScanItems;
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ int wave_min_int(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {

@@ -424,11 +424,55 @@ def _ans_rows(rows_per_stream, m):
   return rows
 
 
+def _ans_bad(what, bad):
+  # _ans_freq saw the same frequencies
+  raise ValueError('%s: the frequencies of column %d do not sum to 2^%d'
+                   % (what, bad - 1, ANS_PROB_BITS))
+
+
+def _ans_streams(packed, offsets, b, rows):
+  """The number of streams of b rows, `rows` each, after the check that
+  `packed` and `offsets` have the shapes of that many."""
+  n = -(-b // rows)
+  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] != n + 1:
+    raise ValueError('packed must be (bytes,) and offsets (%d,) for %d rows in '
+                     'streams of %d, got shapes %s and %s'
+                     % (n + 1, b, rows, tuple(packed.shape),
+                        tuple(offsets.shape)))
+  return n
+
+
+def _raise_ans_skipped(what, status):
+  skipped = int(status[2])
+  if skipped:
+    raise ValueError('%s: %d streams outside the output' % (what, skipped))
+
+
+def _raise_ans_unpack_status(what, bad_tables, status, used, offsets, rows,
+                             exact):
+  """The end of an unpack call, one host read: bad tables (bad_tables(what,
+  bad) raises), malformed streams, and with `exact` streams that leave bytes
+  of their span unread."""
+  n = used.shape[0]
+  loose = used.to(torch.int64) != offsets[1:] - offsets[:-1]
+  report = torch.cat([status, torch.stack([
+      loose.sum(), loose.to(torch.int32).argmax().to(torch.int64)])])
+  malformed, first, bad, loose, first_loose = report.tolist()
+  if bad:
+    bad_tables(what, bad)
+  if malformed:
+    raise ValueError('%s: %d malformed streams of %d, the first is stream %d '
+                     '(rows %d and on)'
+                     % (what, malformed, n, first - 1, (first - 1) * rows))
+  if exact and loose:
+    raise ValueError('%s: %d streams of %d do not use up their span of bytes, '
+                     'the first is stream %d' % (what, loose, n, first_loose))
+
+
 def _raise_ans_status(indices, status, what):
   uncodable, first, bad = status.tolist()
-  if bad:   # _ans_freq saw the same frequencies
-    raise ValueError('%s: the frequencies of column %d do not sum to 2^%d'
-                     % (what, bad - 1, ANS_PROB_BITS))
+  if bad:
+    _ans_bad(what, bad)
   if uncodable:
     row, column = divmod(first - 1, indices.shape[1])
     raise KeyError('%s: column %d has no frequency for index %d (row %d); %d '
@@ -493,10 +537,7 @@ def pack_index_ans(indices, freq, rows_per_stream=None):
       vtc_hip.ptr(sizes), vtc_hip.ptr(offsets), vtc_hip.ptr(packed), total,
       vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
       vtc_hip.current_stream(device)), 'vtc_index_ans_pack')
-  skipped = int(status[2])
-  if skipped:
-    raise ValueError('pack_index_ans: %d streams outside the output'
-                     % skipped)
+  _raise_ans_skipped('pack_index_ans', status)
   return packed, offsets, rows
 
 
@@ -519,12 +560,7 @@ def unpack_index_ans(packed, offsets, freq, b, rows_per_stream, exact=True):
   if b < 1:
     raise ValueError('b must be at least 1')
   rows = _ans_rows(rows_per_stream, m)
-  n = -(-b // rows)
-  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] != n + 1:
-    raise ValueError('packed must be (bytes,) and offsets (%d,) for %d rows in '
-                     'streams of %d, got shapes %s and %s'
-                     % (n + 1, b, rows, tuple(packed.shape),
-                        tuple(offsets.shape)))
+  n = _ans_streams(packed, offsets, b, rows)
   lib = vtc_hip.load_library()
   packed, offsets = packed.contiguous(), offsets.contiguous()
   device = packed.device
@@ -539,21 +575,8 @@ def unpack_index_ans(packed, offsets, freq, b, rows_per_stream, exact=True):
       vtc_hip.ptr(freq), kmax, rows, vtc_hip.ptr(indices), vtc_hip.ptr(used),
       vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
       vtc_hip.current_stream(device)), 'vtc_index_ans_unpack')
-  loose = used.to(torch.int64) != offsets[1:] - offsets[:-1]
-  report = torch.cat([status, torch.stack([
-      loose.sum(), loose.to(torch.int32).argmax().to(torch.int64)])])
-  malformed, first, bad, loose, first_loose = report.tolist()
-  if bad:   # _ans_freq saw the same frequencies
-    raise ValueError('unpack_index_ans: the frequencies of column %d do not '
-                     'sum to 2^%d' % (bad - 1, ANS_PROB_BITS))
-  if malformed:
-    raise ValueError('unpack_index_ans: %d malformed streams of %d, the first '
-                     'is stream %d (rows %d and on)'
-                     % (malformed, n, first - 1, (first - 1) * rows))
-  if exact and loose:
-    raise ValueError('unpack_index_ans: %d streams of %d do not use up their '
-                     'span of bytes, the first is stream %d'
-                     % (loose, n, first_loose))
+  _raise_ans_unpack_status('unpack_index_ans', _ans_bad, status, used, offsets,
+                           rows, exact)
   return indices
 
 
@@ -745,10 +768,7 @@ def pack_index_ans_split(indices, tables, rows_per_stream=None):
       kmax, rows, vtc_hip.ptr(sizes), vtc_hip.ptr(offsets),
       vtc_hip.ptr(packed), total, vtc_hip.ptr(status), vtc_hip.ptr(ws),
       ws.numel(), vtc_hip.current_stream(device)), 'vtc_index_ans_split_pack')
-  skipped = int(status[2])
-  if skipped:
-    raise ValueError('pack_index_ans_split: %d streams outside the output'
-                     % skipped)
+  _raise_ans_skipped('pack_index_ans_split', status)
   return packed, offsets, rows
 
 
@@ -765,12 +785,7 @@ def unpack_index_ans_split(packed, offsets, tables, b, rows_per_stream,
   if b < 1:
     raise ValueError('b must be at least 1')
   rows = _ans_split_rows(rows_per_stream)
-  n = -(-b // rows)
-  if packed.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] != n + 1:
-    raise ValueError('packed must be (bytes,) and offsets (%d,) for %d rows in '
-                     'streams of %d, got shapes %s and %s'
-                     % (n + 1, b, rows, tuple(packed.shape),
-                        tuple(offsets.shape)))
+  n = _ans_streams(packed, offsets, b, rows)
   lib = vtc_hip.load_library()
   packed, offsets = packed.contiguous(), offsets.contiguous()
   device = packed.device
@@ -786,18 +801,6 @@ def unpack_index_ans_split(packed, offsets, tables, b, rows_per_stream,
       vtc_hip.ptr(indices), vtc_hip.ptr(used), vtc_hip.ptr(status),
       vtc_hip.ptr(ws), ws.numel(), vtc_hip.current_stream(device)),
                 'vtc_index_ans_split_unpack')
-  loose = used.to(torch.int64) != offsets[1:] - offsets[:-1]
-  report = torch.cat([status, torch.stack([
-      loose.sum(), loose.to(torch.int32).argmax().to(torch.int64)])])
-  malformed, first, bad, loose, first_loose = report.tolist()
-  if bad:
-    _ans_split_bad('unpack_index_ans_split', bad)
-  if malformed:
-    raise ValueError('unpack_index_ans_split: %d malformed streams of %d, the '
-                     'first is stream %d (rows %d and on)'
-                     % (malformed, n, first - 1, (first - 1) * rows))
-  if exact and loose:
-    raise ValueError('unpack_index_ans_split: %d streams of %d do not use up '
-                     'their span of bytes, the first is stream %d'
-                     % (loose, n, first_loose))
+  _raise_ans_unpack_status('unpack_index_ans_split', _ans_split_bad, status,
+                           used, offsets, rows, exact)
   return indices
