@@ -42,6 +42,13 @@ two symbols, i >> 8 and i & 255, under the same states
   unpack_index_ans_split        (packed, offsets), tables, b, rows_per_stream
                                 -> indices [b]
 
+The R-D points of utils.quantization and utils.vector_quantization name none
+of these functions.  Each source code is described once, at the end of this
+module (Entropy, Huffman, Ans and AnsSplit, by name in SOURCE_CODES): its
+symbol limit, what its tables are called, and train / total_bits / pack /
+unpack.  Packed streams travel as a StreamSet, whose total is in bits whatever
+its coder's offsets count; the two range coders' wrappers share one body.
+
 The per-entry work runs in the kernels of csrc/index_code.hip behind
 include/vtc_index_code.h, for the way back of
 csrc/index_decode.hip behind include/vtc_index_decode.h, and
@@ -49,6 +56,8 @@ of csrc/index_ans.hip and csrc/index_ans_split.hip.  Indices are (b, m) int32
 device tensors: m index streams ("columns") per row, each with a table of its
 own, {int index: str of '0' / '1'}, or a row of frequencies.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -79,6 +88,22 @@ def _host_rows(counts):
   return rows
 
 
+def _in_use(k, m, kmax):
+  """The codewords in use of m columns of kmax slots as m ints: k as
+  index_huffman_tables takes it."""
+  if k is None:
+    k = [kmax] * m
+  else:
+    if torch.is_tensor(k):
+      k = k.cpu().numpy()
+    k = [int(v) for v in np.asarray(k).reshape(-1)]
+    if len(k) == 1:
+      k = k * m
+  if len(k) != m or min(k) < 1 or max(k) > kmax:
+    raise ValueError('k must hold %d values in [1, %d]' % (m, kmax))
+  return k
+
+
 def index_huffman_tables(counts, k=None):
   """One Huffman table per column: a list of m dicts {index: codeword}.
 
@@ -97,16 +122,7 @@ def index_huffman_tables(counts, k=None):
   k[j] = 1 gets {0: ''}, a code of no bits."""
   rows = _host_rows(counts)
   m, kmax = len(rows), len(rows[0])
-  if k is None:
-    k = [kmax] * m
-  else:
-    if torch.is_tensor(k):
-      k = k.cpu().numpy()
-    k = [int(v) for v in np.asarray(k).reshape(-1)]
-    if len(k) == 1:
-      k = k * m
-  if len(k) != m or min(k) < 1 or max(k) > kmax:
-    raise ValueError('k must hold %d values in [1, %d]' % (m, kmax))
+  k = _in_use(k, m, kmax)
   return [jpeg.compute_huffman_table(
       {i: (row[i] if row[i] > 0 else 1) for i in range(k[j])})
           for j, row in enumerate(rows)]
@@ -338,16 +354,7 @@ def index_ans_frequencies(counts, k=None):
   m, kmax = len(rows), len(rows[0])
   if kmax > MAX_SYMBOLS:
     raise NotImplementedError('kmax = %d, at most %d' % (kmax, MAX_SYMBOLS))
-  if k is None:
-    k = [kmax] * m
-  else:
-    if torch.is_tensor(k):
-      k = k.cpu().numpy()
-    k = [int(v) for v in np.asarray(k).reshape(-1)]
-    if len(k) == 1:
-      k = k * m
-  if len(k) != m or min(k) < 1 or max(k) > kmax:
-    raise ValueError('k must hold %d values in [1, %d]' % (m, kmax))
+  k = _in_use(k, m, kmax)
   freq = np.zeros((m, kmax), dtype=np.uint16)
   for j, row in enumerate(rows):
     kj = k[j]
@@ -480,15 +487,95 @@ def _raise_ans_status(indices, status, what):
                                      row, uncodable))
 
 
-def _ans_sizes(lib, indices, freq, kmax, rows, ws, status):
-  b, m = indices.shape
-  device = indices.device
+def _ans_columns(freq):
+  host = freq.cpu().numpy() if torch.is_tensor(freq) else np.asarray(freq)
+  return 1 if host.ndim == 1 else host.shape[0]
+
+
+# What the shared body of the two range coders' wrappers asks of a coder: the
+# prefix `entry` of its C entry points; many_columns, whether they take m (the
+# split coder has one column); indices -> the tensor the calls read; columns:
+# tables -> m; tables: (tables, m, device) -> the checked tables as device
+# tensors, then kmax; rows: (rows_per_stream, m) -> the rows of a stream; the
+# raisers raise_status(indices, status, what) and raise_bad(what, bad).
+_RangeCalls = collections.namedtuple(
+    '_RangeCalls', 'entry many_columns indices columns tables rows '
+    'raise_status raise_bad')
+
+
+def _range_tables(coder, lib, tables, m, device):
+  """(the device tables, kept alive for the calls; what every C call takes
+  between b and the rows of a stream: [m,] the tables' pointers, kmax; the
+  workspace; the status word)."""
+  *held, kmax = coder.tables(tables, m, device)
+  dims = (m,) if coder.many_columns else ()
+  ws = vtc_hip.workspace(
+      getattr(lib, coder.entry + '_workspace_bytes')(*dims, kmax), device)
+  status = torch.empty(3, dtype=torch.int64, device=device)
+  return (held, dims + tuple(vtc_hip.ptr(t) for t in held) + (kmax,), ws,
+          status)
+
+
+def _range_encode(coder, what, indices, tables, rows_per_stream, pack):
+  """The body of index_ans[_split]_stream_bytes (pack false: the sizes) and
+  of pack_index_ans[_split] (pack true: packed, offsets, rows)."""
+  lib = vtc_hip.load_library()
+  indices = coder.indices(indices)
+  b, device = indices.shape[0], indices.device
+  m = indices.shape[1] if coder.many_columns else 1
+  rows = coder.rows(rows_per_stream, m)
+  held, middle, ws, status = _range_tables(coder, lib, tables, m, device)
+  stream = vtc_hip.current_stream(device)
   sizes = torch.empty(-(-b // rows), dtype=torch.int32, device=device)
-  vtc_hip.check(lib.vtc_index_ans_sizes(
-      vtc_hip.ptr(indices), b, m, vtc_hip.ptr(freq), kmax, rows,
-      vtc_hip.ptr(sizes), vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
-      vtc_hip.current_stream(device)), 'vtc_index_ans_sizes')
-  return sizes
+  vtc_hip.check(getattr(lib, coder.entry + '_sizes')(
+      vtc_hip.ptr(indices), b, *middle, rows, vtc_hip.ptr(sizes),
+      vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(), stream),
+                coder.entry + '_sizes')
+  coder.raise_status(indices, status, what)
+  if not pack:
+    return sizes
+  offsets = jpeg.bit_offsets(sizes)   # a plain prefix sum: of bytes here
+  total = int(offsets[-1])
+  packed = torch.empty(total, dtype=torch.uint8, device=device)
+  vtc_hip.check(getattr(lib, coder.entry + '_pack')(
+      vtc_hip.ptr(indices), b, *middle, rows, vtc_hip.ptr(sizes),
+      vtc_hip.ptr(offsets), vtc_hip.ptr(packed), total, vtc_hip.ptr(status),
+      vtc_hip.ptr(ws), ws.numel(), stream), coder.entry + '_pack')
+  _raise_ans_skipped(what, status)
+  return packed, offsets, rows
+
+
+def _range_unpack(coder, what, packed, offsets, tables, b, rows_per_stream,
+                  exact):
+  """The body of unpack_index_ans[_split]."""
+  packed = vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
+  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
+  b = int(b)
+  m = coder.columns(tables)
+  if b < 1:
+    raise ValueError('b must be at least 1')
+  rows = coder.rows(rows_per_stream, m)
+  n = _ans_streams(packed, offsets, b, rows)
+  lib = vtc_hip.load_library()
+  packed, offsets = packed.contiguous(), offsets.contiguous()
+  device = packed.device
+  held, middle, ws, status = _range_tables(coder, lib, tables, m, device)
+  indices = torch.empty((b, m) if coder.many_columns else b,
+                        dtype=torch.int32, device=device)
+  used = torch.empty(n, dtype=torch.int32, device=device)
+  bytes_from = packed if packed.numel() else ws   # never read when empty
+  vtc_hip.check(getattr(lib, coder.entry + '_unpack')(
+      vtc_hip.ptr(bytes_from), packed.numel(), vtc_hip.ptr(offsets), b,
+      *middle, rows, vtc_hip.ptr(indices), vtc_hip.ptr(used),
+      vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), coder.entry + '_unpack')
+  _raise_ans_unpack_status(what, coder.raise_bad, status, used, offsets, rows,
+                           exact)
+  return indices
+
+
+_ANS = _RangeCalls('vtc_index_ans', True, _indices, _ans_columns, _ans_freq,
+                   _ans_rows, _raise_ans_status, _ans_bad)
 
 
 def index_ans_stream_bytes(indices, freq, rows_per_stream=None):
@@ -498,16 +585,8 @@ def index_ans_stream_bytes(indices, freq, rows_per_stream=None):
   which puts the 256-byte flush at about 0.03 bit per index.  One host read
   (the status).  An index of frequency 0 (the -1 of a NaN code among them)
   raises KeyError naming the column and the index."""
-  lib = vtc_hip.load_library()
-  indices = _indices(indices)
-  m, device = indices.shape[1], indices.device
-  rows = _ans_rows(rows_per_stream, m)
-  freq, kmax = _ans_freq(freq, m, device)
-  ws = vtc_hip.workspace(lib.vtc_index_ans_workspace_bytes(m, kmax), device)
-  status = torch.empty(3, dtype=torch.int64, device=device)
-  sizes = _ans_sizes(lib, indices, freq, kmax, rows, ws, status)
-  _raise_ans_status(indices, status, 'index_ans_stream_bytes')
-  return sizes
+  return _range_encode(_ANS, 'index_ans_stream_bytes', indices, freq,
+                       rows_per_stream, False)
 
 
 def pack_index_ans(indices, freq, rows_per_stream=None):
@@ -518,27 +597,8 @@ def pack_index_ans(indices, freq, rows_per_stream=None):
   index_ans_stream_bytes when None), which the decoder needs again.  Stream s
   holds rows s * rows_per_stream and on in row-major order
   (include/vtc_index_ans.h)."""
-  from utils import jpeg
-  lib = vtc_hip.load_library()
-  indices = _indices(indices)
-  b, m = indices.shape
-  device = indices.device
-  rows = _ans_rows(rows_per_stream, m)
-  freq, kmax = _ans_freq(freq, m, device)
-  ws = vtc_hip.workspace(lib.vtc_index_ans_workspace_bytes(m, kmax), device)
-  status = torch.empty(3, dtype=torch.int64, device=device)
-  sizes = _ans_sizes(lib, indices, freq, kmax, rows, ws, status)
-  _raise_ans_status(indices, status, 'pack_index_ans')
-  offsets = jpeg.bit_offsets(sizes)   # a plain prefix sum: bytes here
-  total = int(offsets[-1])
-  packed = torch.empty(total, dtype=torch.uint8, device=device)
-  vtc_hip.check(lib.vtc_index_ans_pack(
-      vtc_hip.ptr(indices), b, m, vtc_hip.ptr(freq), kmax, rows,
-      vtc_hip.ptr(sizes), vtc_hip.ptr(offsets), vtc_hip.ptr(packed), total,
-      vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
-      vtc_hip.current_stream(device)), 'vtc_index_ans_pack')
-  _raise_ans_skipped('pack_index_ans', status)
-  return packed, offsets, rows
+  return _range_encode(_ANS, 'pack_index_ans', indices, freq, rows_per_stream,
+                       True)
 
 
 def unpack_index_ans(packed, offsets, freq, b, rows_per_stream, exact=True):
@@ -552,32 +612,8 @@ def unpack_index_ans(packed, offsets, freq, b, rows_per_stream, exact=True):
   slot without its 256 bytes of states, a stream that runs out of words, end
   states that are not 2^16) and, with exact=True, for streams that leave bytes
   of their span unread.  VtcHipError for a CPU tensor.  One host read."""
-  packed = vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
-  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
-  b = int(b)
-  host_freq = freq.cpu().numpy() if torch.is_tensor(freq) else np.asarray(freq)
-  m = 1 if host_freq.ndim == 1 else host_freq.shape[0]
-  if b < 1:
-    raise ValueError('b must be at least 1')
-  rows = _ans_rows(rows_per_stream, m)
-  n = _ans_streams(packed, offsets, b, rows)
-  lib = vtc_hip.load_library()
-  packed, offsets = packed.contiguous(), offsets.contiguous()
-  device = packed.device
-  freq, kmax = _ans_freq(host_freq, m, device)
-  indices = torch.empty((b, m), dtype=torch.int32, device=device)
-  used = torch.empty(n, dtype=torch.int32, device=device)
-  status = torch.empty(3, dtype=torch.int64, device=device)
-  ws = vtc_hip.workspace(lib.vtc_index_ans_workspace_bytes(m, kmax), device)
-  bytes_from = packed if packed.numel() else ws   # never read when empty
-  vtc_hip.check(lib.vtc_index_ans_unpack(
-      vtc_hip.ptr(bytes_from), packed.numel(), vtc_hip.ptr(offsets), b, m,
-      vtc_hip.ptr(freq), kmax, rows, vtc_hip.ptr(indices), vtc_hip.ptr(used),
-      vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
-      vtc_hip.current_stream(device)), 'vtc_index_ans_unpack')
-  _raise_ans_unpack_status('unpack_index_ans', _ans_bad, status, used, offsets,
-                           rows, exact)
-  return indices
+  return _range_unpack(_ANS, 'unpack_index_ans', packed, offsets, freq, b,
+                       rows_per_stream, exact)
 
 
 # ------------------------------------- range coding, more than 4096 symbols
@@ -686,7 +722,7 @@ def _ans_split_column(indices):
   return indices.contiguous()
 
 
-def _ans_split_rows(rows_per_stream):
+def _ans_split_rows(rows_per_stream, m=1):
   if rows_per_stream is None:
     return ANS_SPLIT_ROWS
   rows = int(rows_per_stream)
@@ -714,16 +750,10 @@ def _raise_ans_split_status(indices, status, what):
                    % (what, int(indices[first - 1]), first - 1, uncodable))
 
 
-def _ans_split_sizes(lib, indices, tables, rows, ws, status):
-  freq_hi, freq_lo, kmax = tables
-  b, device = indices.shape[0], indices.device
-  sizes = torch.empty(-(-b // rows), dtype=torch.int32, device=device)
-  vtc_hip.check(lib.vtc_index_ans_split_sizes(
-      vtc_hip.ptr(indices), b, vtc_hip.ptr(freq_hi), vtc_hip.ptr(freq_lo),
-      kmax, rows, vtc_hip.ptr(sizes), vtc_hip.ptr(status), vtc_hip.ptr(ws),
-      ws.numel(), vtc_hip.current_stream(device)),
-                'vtc_index_ans_split_sizes')
-  return sizes
+_ANS_SPLIT = _RangeCalls(
+    'vtc_index_ans_split', False, _ans_split_column, lambda tables: 1,
+    lambda tables, m, device: _ans_split_tables(tables, device),
+    _ans_split_rows, _raise_ans_split_status, _ans_split_bad)
 
 
 def index_ans_split_stream_bytes(indices, tables, rows_per_stream=None):
@@ -733,43 +763,16 @@ def index_ans_split_stream_bytes(indices, tables, rows_per_stream=None):
   (the status).  An index without a frequency (the -1 of a NaN code among
   them) raises KeyError naming its row and the index; tables whose sums are
   not 2^15 raise ValueError before any device work."""
-  lib = vtc_hip.load_library()
-  indices = _ans_split_column(indices)
-  device = indices.device
-  rows = _ans_split_rows(rows_per_stream)
-  tables = _ans_split_tables(tables, device)
-  ws = vtc_hip.workspace(
-      lib.vtc_index_ans_split_workspace_bytes(tables[2]), device)
-  status = torch.empty(3, dtype=torch.int64, device=device)
-  sizes = _ans_split_sizes(lib, indices, tables, rows, ws, status)
-  _raise_ans_split_status(indices, status, 'index_ans_split_stream_bytes')
-  return sizes
+  return _range_encode(_ANS_SPLIT, 'index_ans_split_stream_bytes', indices,
+                       tables, rows_per_stream, False)
 
 
 def pack_index_ans_split(indices, tables, rows_per_stream=None):
   """(packed, offsets, rows_per_stream) of the [b] indices under tables =
   (freq_hi, freq_lo): what pack_index_ans returns, for the streams of
   include/ext/vtc_index_ans_split.h."""
-  lib = vtc_hip.load_library()
-  indices = _ans_split_column(indices)
-  b, device = indices.shape[0], indices.device
-  rows = _ans_split_rows(rows_per_stream)
-  tables = _ans_split_tables(tables, device)
-  freq_hi, freq_lo, kmax = tables
-  ws = vtc_hip.workspace(lib.vtc_index_ans_split_workspace_bytes(kmax), device)
-  status = torch.empty(3, dtype=torch.int64, device=device)
-  sizes = _ans_split_sizes(lib, indices, tables, rows, ws, status)
-  _raise_ans_split_status(indices, status, 'pack_index_ans_split')
-  offsets = jpeg.bit_offsets(sizes)   # a plain prefix sum: bytes here
-  total = int(offsets[-1])
-  packed = torch.empty(total, dtype=torch.uint8, device=device)
-  vtc_hip.check(lib.vtc_index_ans_split_pack(
-      vtc_hip.ptr(indices), b, vtc_hip.ptr(freq_hi), vtc_hip.ptr(freq_lo),
-      kmax, rows, vtc_hip.ptr(sizes), vtc_hip.ptr(offsets),
-      vtc_hip.ptr(packed), total, vtc_hip.ptr(status), vtc_hip.ptr(ws),
-      ws.numel(), vtc_hip.current_stream(device)), 'vtc_index_ans_split_pack')
-  _raise_ans_skipped('pack_index_ans_split', status)
-  return packed, offsets, rows
+  return _range_encode(_ANS_SPLIT, 'pack_index_ans_split', indices, tables,
+                       rows_per_stream, True)
 
 
 def unpack_index_ans_split(packed, offsets, tables, b, rows_per_stream,
@@ -779,28 +782,114 @@ def unpack_index_ans_split(packed, offsets, tables, b, rows_per_stream,
   device work), for malformed streams and, with exact=True, for streams that
   leave bytes of their span unread; VtcHipError for a CPU tensor.  One host
   read."""
-  packed = vtc_hip.require_device_tensor(packed, 'packed', torch.uint8)
-  offsets = vtc_hip.require_device_tensor(offsets, 'offsets', torch.int64)
-  b = int(b)
-  if b < 1:
-    raise ValueError('b must be at least 1')
-  rows = _ans_split_rows(rows_per_stream)
-  n = _ans_streams(packed, offsets, b, rows)
-  lib = vtc_hip.load_library()
-  packed, offsets = packed.contiguous(), offsets.contiguous()
-  device = packed.device
-  freq_hi, freq_lo, kmax = _ans_split_tables(tables, device)
-  indices = torch.empty(b, dtype=torch.int32, device=device)
-  used = torch.empty(n, dtype=torch.int32, device=device)
-  status = torch.empty(3, dtype=torch.int64, device=device)
-  ws = vtc_hip.workspace(lib.vtc_index_ans_split_workspace_bytes(kmax), device)
-  bytes_from = packed if packed.numel() else ws   # never read when empty
-  vtc_hip.check(lib.vtc_index_ans_split_unpack(
-      vtc_hip.ptr(bytes_from), packed.numel(), vtc_hip.ptr(offsets), b,
-      vtc_hip.ptr(freq_hi), vtc_hip.ptr(freq_lo), kmax, rows,
-      vtc_hip.ptr(indices), vtc_hip.ptr(used), vtc_hip.ptr(status),
-      vtc_hip.ptr(ws), ws.numel(), vtc_hip.current_stream(device)),
-                'vtc_index_ans_split_unpack')
-  _raise_ans_unpack_status('unpack_index_ans_split', _ans_split_bad, status,
-                           used, offsets, rows, exact)
-  return indices
+  return _range_unpack(_ANS_SPLIT, 'unpack_index_ans_split', packed, offsets,
+                       tables, b, rows_per_stream, exact)
+
+
+# ------------------------------------------------ the source codes, described
+# One set of index streams with what its decoder needs beside the tables:
+# packed and offsets of the coder's pack function, the rows b and
+# rows_per_stream (both None for Huffman streams, one per row, that come from
+# outside) and the total in BITS (None for a set from outside).  Whether the
+# offsets count bits or bytes is the coder's business alone.
+StreamSet = collections.namedtuple(
+    'StreamSet', 'packed offsets b rows_per_stream bits')
+
+
+class Entropy(object):
+  """source_code 'entropy': the empirical entropy of the indices, a figure
+  (quantization.entropy_bits of their counts) and no code.  No tables, no
+  streams, any number of symbols."""
+  name = 'entropy'
+  max_symbols = float('inf')
+  one_column = False
+  has_tables = writes_streams = False
+
+
+class _TableCode(object):
+  """What the R-D points of utils.quantization and utils.vector_quantization
+  ask of a source code with tables, no instance state: its name; max_symbols,
+  the most a column may have; one_column, whether it takes [b] indices and not
+  (b, m); tables_noun, its tables in the missing-tables message; and
+    train(counts, k) -> tables
+    total_bits(indices, tables, rows_per_stream), nothing written
+    pack(indices, tables, rows_per_stream) -> StreamSet
+    unpack(streams, tables) -> indices"""
+  has_tables = writes_streams = True
+
+  @classmethod
+  def train_column(cls, counts, k):
+    """The tables of one column from its [kmax] counts."""
+    tables = cls.train(counts, k)
+    return tables if cls.one_column else tables[0]
+
+
+class Huffman(_TableCode):
+  """source_code 'huffman': one prefix code per column; a stream per row,
+  offsets in bits."""
+  name = 'huffman'
+  max_symbols = MAX_SYMBOLS
+  one_column = False
+  tables_noun = 'the Huffman tables'
+  train = staticmethod(index_huffman_tables)
+
+  @staticmethod
+  def total_bits(indices, tables, rows_per_stream=None):
+    return int(index_code_bits(indices, tables)[1].sum())
+
+  @staticmethod
+  def pack(indices, tables, rows_per_stream=None):
+    packed, offsets = pack_index_streams(indices, tables)
+    return StreamSet(packed, offsets, indices.shape[0], None,
+                     int(offsets[-1]))
+
+  @staticmethod
+  def unpack(streams, tables):
+    return unpack_index_streams(streams.packed, streams.offsets, tables)
+
+
+class _RangeCode(_TableCode):
+  """A range coder: streams of rows_per_stream rows, offsets in bytes, from
+  its three wrappers stream_bytes, pack_streams and unpack_streams."""
+  tables_noun = 'the frequencies'
+
+  @classmethod
+  def total_bits(cls, indices, tables, rows_per_stream=None):
+    return 8 * int(cls.stream_bytes(indices, tables, rows_per_stream).sum())
+
+  @classmethod
+  def pack(cls, indices, tables, rows_per_stream=None):
+    packed, offsets, rows = cls.pack_streams(indices, tables, rows_per_stream)
+    return StreamSet(packed, offsets, indices.shape[0], rows,
+                     8 * int(offsets[-1]))
+
+  @classmethod
+  def unpack(cls, streams, tables):
+    return cls.unpack_streams(streams.packed, streams.offsets, tables,
+                              streams.b, streams.rows_per_stream)
+
+
+class Ans(_RangeCode):
+  """source_code 'ans': one row of frequencies per column."""
+  name = 'ans'
+  max_symbols = MAX_SYMBOLS
+  one_column = False
+  train = staticmethod(index_ans_frequencies)
+  stream_bytes = staticmethod(index_ans_stream_bytes)
+  pack_streams = staticmethod(pack_index_ans)
+  unpack_streams = staticmethod(unpack_index_ans)
+
+
+class AnsSplit(_RangeCode):
+  """source_code 'ans_split': the one column of the large vector quantiser's
+  index under (freq_hi, freq_lo)."""
+  name = 'ans_split'
+  max_symbols = ANS_SPLIT_MAX_SYMBOLS
+  one_column = True
+  train = staticmethod(index_ans_split_frequencies)
+  stream_bytes = staticmethod(index_ans_split_stream_bytes)
+  pack_streams = staticmethod(pack_index_ans_split)
+  unpack_streams = staticmethod(unpack_index_ans_split)
+
+
+SOURCE_CODES = {code.name: code for code in (Entropy, Huffman, Ans, AnsSplit)}

@@ -38,9 +38,11 @@ this module: `from utils import vector_quantization as quantization`.
 
 The rate of a point is the cost of the JPEG source code, the empirical entropy
 of the indices (the default of the baseline and Mod entries) or, with
-source_code='huffman', the bits of the indices under Huffman tables that may
-have been trained on other data (utils.index_coding, include/vtc_index_code.h,
-DESIGN.md 4.17).
+source_code='huffman' or 'ans', the bits of the indices under Huffman tables
+or range-coder frequencies that may have been trained on other data
+(DESIGN.md 4.17, 4.19).  The entry points take a source code with tables as
+its description in utils.index_coding.SOURCE_CODES and follow one path: train
+when no tables are given, then total the bits, or pack, unpack and dequantise.
 """
 import ctypes
 
@@ -48,6 +50,7 @@ import numpy as np
 import torch
 
 import vtc_hip
+from utils import index_coding as _coding
 
 MAX_CODEWORDS = vtc_hip.QUANT_MAX_CODEWORDS
 
@@ -406,10 +409,7 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
   'SSIM'} of the images, with the patch figure under 'pSNR_patches'.
   """
   from utils import jpeg
-  if source_code not in ('jpeg', 'entropy', 'huffman', 'ans'):
-    raise ValueError("source_code must be 'jpeg', 'entropy', 'huffman' or "
-                     "'ans'")
-  _check_from_stream(from_stream, source_code)
+  coder = _source_coder(source_code, from_stream, jpeg=True)
   codes = _codes(codes)
   patches = _codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
@@ -436,32 +436,21 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
       tables = jpeg.tables_from_counts(*jpeg.symbol_counts(levels))
     bits = jpeg.stream_bits(levels, tables[0], tables[1])
     total_bits = int(jpeg.bit_offsets(bits)[-1])
-  elif source_code == 'huffman':
-    if int(status) != 0:   # before the coder meets their index -1
-      raise ValueError('compute_RD_point: the codes hold NaN')
-    counts_and_k = lambda: (index_counts(indices, pair[0].shape[1]), pair[1])
-    if from_stream:
-      total_bits, tables, streams = _huffman_streams(indices, tables,
-                                                     counts_and_k)
-      reconstruction = _reconstruct(decode_codes(*streams, tables, pair),
-                                    dictionary)
-    else:
-      total_bits, tables = _huffman_bits(indices, tables, counts_and_k)
-  elif source_code == 'ans':
-    if int(status) != 0:   # before the coder meets their index -1
-      raise ValueError('compute_RD_point: the codes hold NaN')
-    counts_and_k = lambda: (index_counts(indices, pair[0].shape[1]), pair[1])
-    if from_stream:
-      total_bits, tables, streams = _ans_streams(indices, tables, counts_and_k,
-                                                 rows_per_stream)
-      reconstruction = _reconstruct(
-          decode_codes(streams[0], streams[1], tables, pair,
-                       ans_shape=(indices.shape[0], streams[2])), dictionary)
-    else:
-      total_bits, tables = _ans_bits(indices, tables, counts_and_k,
-                                     rows_per_stream)
-  else:
+  elif not coder.has_tables:
     total_bits = entropy_bits(index_counts(indices, pair[0].shape[1]))
+  else:
+    if int(status) != 0:   # before the coder meets their index -1
+      raise ValueError('compute_RD_point: the codes hold NaN')
+    if tables is None:
+      tables = coder.train(index_counts(indices, pair[0].shape[1]), pair[1])
+    if from_stream:
+      streams = coder.pack(indices, tables, rows_per_stream)
+      total_bits = streams.bits
+      reconstruction = _reconstruct(
+          dequantize_assignments(coder.unpack(streams, tables), pair),
+          dictionary)
+    else:
+      total_bits = coder.total_bits(indices, tables, rows_per_stream)
   if int(status) != 0:
     raise ValueError('compute_RD_point: the codes hold NaN')
   rate = total_bits / float(patches.numel())
@@ -469,64 +458,35 @@ def compute_RD_point(codes, patches, dictionary, codebooks, lengths=None,
                            fullimg_reshape_params), tables
 
 
-def _huffman_bits(indices, tables, counts_and_k):
-  """(total bits of the (b, m) indices under `tables`, the tables): a list of
-  m dicts, trained on counts_and_k() = (counts (m, kmax), k [m]) when None."""
-  from utils import index_coding
-  if tables is None:
-    tables = index_coding.index_huffman_tables(*counts_and_k())
-  _, column_bits = index_coding.index_code_bits(indices, tables)
-  return int(column_bits.sum()), tables
-
-
-def _huffman_streams(indices, tables, counts_and_k):
-  """_huffman_bits from the packed streams: (their total bits, the tables,
-  (packed, offsets))."""
-  from utils import index_coding
-  if tables is None:
-    tables = index_coding.index_huffman_tables(*counts_and_k())
-  packed, offsets = index_coding.pack_index_streams(indices, tables)
-  return int(offsets[-1]), tables, (packed, offsets)
-
-
-def _ans_bits(indices, tables, counts_and_k, rows_per_stream):
-  """(8 x the bytes of the range-coded streams of the (b, m) indices, the
-  frequencies): a uint16 (m, kmax) array, trained on counts_and_k() when
-  None."""
-  from utils import index_coding
-  if tables is None:
-    tables = index_coding.index_ans_frequencies(*counts_and_k())
-  sizes = index_coding.index_ans_stream_bytes(indices, tables, rows_per_stream)
-  return 8 * int(sizes.sum()), tables
-
-
-def _ans_streams(indices, tables, counts_and_k, rows_per_stream):
-  """_ans_bits from the packed streams: (their total bits, the frequencies,
-  (packed, offsets, rows_per_stream))."""
-  from utils import index_coding
-  if tables is None:
-    tables = index_coding.index_ans_frequencies(*counts_and_k())
-  streams = index_coding.pack_index_ans(indices, tables, rows_per_stream)
-  return 8 * int(streams[1][-1]), tables, streams
-
-
-# the source codes that have tables and write streams of indices
-_TABLE_CODES = ('huffman', 'ans')
-
-
-def _check_from_stream(from_stream, source_code):
-  if from_stream and source_code not in _TABLE_CODES:
+def _source_coder(source_code, from_stream, jpeg=False, mixed=False):
+  """The description of `source_code` in index_coding.SOURCE_CODES, after the
+  checks every R-D entry point makes of the name: None for 'jpeg' where the
+  entry point takes it (it codes levels, not indices, and has no description);
+  ValueError for any other name without one and, outside the mixed points,
+  for a code of a single column; ValueError for from_stream with a code that
+  writes no streams of indices."""
+  coder = None
+  if not (jpeg and source_code == 'jpeg'):
+    coder = _coding.SOURCE_CODES.get(source_code)
+    if coder is None or (coder.one_column and not mixed):
+      raise ValueError("source_code must be %s'entropy', 'huffman' or 'ans'"
+                       % ("'jpeg', " if jpeg else ''))
+  if from_stream and not (coder and coder.writes_streams):
     raise ValueError("from_stream=True needs source_code='huffman' or 'ans': "
                      'only those source codes write streams of indices')
+  return coder
 
 
-def _unpack_indices(packed, offsets, tables, ans_shape):
-  from utils import index_coding
+def _stream_set(packed, offsets, ans_shape):
+  """(coder, stream set) of what the public decoders are given: Huffman
+  streams, or with ans_shape = (b, rows_per_stream) those of the range
+  coder."""
   if ans_shape is None:
-    return index_coding.unpack_index_streams(packed, offsets, tables)
+    return _coding.Huffman, _coding.StreamSet(packed, offsets, None, None,
+                                              None)
   b, rows_per_stream = ans_shape
-  return index_coding.unpack_index_ans(packed, offsets, tables, b,
-                                       rows_per_stream)
+  return _coding.Ans, _coding.StreamSet(packed, offsets, b, rows_per_stream,
+                                        None)
 
 
 def decode_codes(packed, offsets, tables, codebooks, ans_shape=None):
@@ -539,24 +499,15 @@ def decode_codes(packed, offsets, tables, codebooks, ans_shape=None):
   ans_shape = (b, rows_per_stream): (packed, offsets) are the range-coded
   streams of index_coding.pack_index_ans instead, `tables` the uint16 (s,
   kmax) frequencies, and index_coding.unpack_index_ans reads them."""
-  return dequantize_assignments(
-      _unpack_indices(packed, offsets, tables, ans_shape), codebooks)
+  coder, streams = _stream_set(packed, offsets, ans_shape)
+  return dequantize_assignments(coder.unpack(streams, tables), codebooks)
 
 
-def _check_source_code(source_code):
-  if source_code not in ('entropy',) + _TABLE_CODES:
-    raise ValueError("source_code must be 'entropy', 'huffman' or 'ans'")
-
-
-def _need_tables(who, *tables, source_code='huffman'):
+def _need_tables(who, coder, *tables):
   if any(table is None for table in tables):
-    if source_code == 'ans':
-      raise ValueError("%s: source_code='ans' with precomputed codebooks "
-                       'needs the frequencies of the training call as well'
-                       % who)
-    raise ValueError("%s: source_code='huffman' with precomputed codebooks "
-                     'needs the Huffman tables of the training call as well'
-                     % who)
+    raise ValueError('%s: source_code=%r with precomputed codebooks needs %s '
+                     'of the training call as well'
+                     % (who, coder.name, coder.tables_noun))
 
 
 def _uniform_for(codes, binwidths, quant_multiplier):
@@ -623,23 +574,21 @@ def baseline_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   source_code 'ans': as 'huffman' with the range coder of compute_RD_point;
   huff_tab1 is then the uint16 (s, kmax) frequency array, and rows_per_stream
   is that of compute_RD_point."""
-  _check_source_code(source_code)
-  _check_from_stream(from_stream, source_code)
+  coder = _source_coder(source_code, from_stream)
   training = precomputed_codebook is None
-  if source_code in _TABLE_CODES and not training:
-    _need_tables('baseline_compute_RD_point', precomputed_huff_tab1,
-                 source_code=source_code)
+  if coder.has_tables and not training:
+    _need_tables('baseline_compute_RD_point', coder, precomputed_huff_tab1)
   codebook = (_uniform_for(codes, binwidths, quant_multiplier) if training
               else precomputed_codebook)
   rate, distortion, tables = compute_RD_point(
       codes, patches, dictionary, codebook, source_code=source_code,
-      tables=(precomputed_huff_tab1 if source_code in _TABLE_CODES and
-              not training else None),
+      tables=(precomputed_huff_tab1 if coder.has_tables and not training
+              else None),
       fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream,
       rows_per_stream=rows_per_stream)
   if training:
     return (rate, distortion, codebook,
-            tables if source_code in _TABLE_CODES else None, None)
+            tables if coder.has_tables else None, None)
   return rate, distortion
 
 
@@ -665,12 +614,10 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   test call takes them back as precomputed_huff_tab1 (ValueError without
   them), as baseline_compute_RD_point does; from_stream likewise, and
   source_code='ans' with rows_per_stream (huff_tab1 the frequency array)."""
-  _check_source_code(source_code)
-  _check_from_stream(from_stream, source_code)
+  coder = _source_coder(source_code, from_stream)
   training = precomputed_codebook is None
-  if source_code in _TABLE_CODES and not training:
-    _need_tables('Mod1_compute_RD_point', precomputed_huff_tab1,
-                 source_code=source_code)
+  if coder.has_tables and not training:
+    _need_tables('Mod1_compute_RD_point', coder, precomputed_huff_tab1)
   if training:
     fit = scalar_lloyd(codes, _uniform_for(codes, init_binwidths, 1.0),
                        lagrange_mult=quant_multiplier,
@@ -681,11 +628,11 @@ def Mod1_compute_RD_point(codes, patches, dictionary, quant_multiplier=1.0,
   rate, distortion, tables = compute_RD_point(
       codes, patches, dictionary, codebook, lengths=lengths,
       lagrange_mult=quant_multiplier, source_code=source_code,
-      tables=(precomputed_huff_tab1 if source_code in _TABLE_CODES and
-              not training else None),
+      tables=(precomputed_huff_tab1 if coder.has_tables and not training
+              else None),
       fullimg_reshape_params=fullimg_reshape_params, from_stream=from_stream,
       rows_per_stream=rows_per_stream)
   if training:
     return (rate, distortion, codebook, lengths,
-            tables if source_code in _TABLE_CODES else None)
+            tables if coder.has_tables else None)
   return rate, distortion

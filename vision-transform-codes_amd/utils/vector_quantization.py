@@ -23,6 +23,8 @@ raises NotImplementedError naming the limit in force.  Index coding stops at
 4096 slots, which trim_vector_codebook makes of a fit that ended there.
 source_code 'ans_split' codes the vector index under the split range coder of
 include/ext/vtc_index_ans_split.h instead, whatever the codebook's size.
+Which coder codes the scalar columns and which the vector column, in one
+stream set or two, is the table _MIXED_CODES; the mixed point has one path.
 
 A vector quantiser of (b, d) vectors is described by
   codebook   float64 (kmax, d)  the codewords; the slots past k are never read
@@ -44,11 +46,13 @@ and gathers its single host read through one float64 torch.cat.  Everything
 else torch does is plumbing: column gathers, index_copy_, views.
 """
 import ctypes
+from collections import namedtuple as _namedtuple
 
 import numpy as np
 import torch
 
 import vtc_hip
+from utils import index_coding as _coding
 from utils import quantization as _scalar
 from utils.quantization import *   # noqa: F401,F403  (a superset of it)
 from utils.quantization import (   # noqa: F401  the names the experiment uses
@@ -351,29 +355,6 @@ def _slots(codebook):
   return int(codebook.shape[0])
 
 
-def _check_table_code(source_code, vec_codebook):
-  if (source_code in _scalar._TABLE_CODES and
-      _slots(vec_codebook) > VQ_MAX_CODEWORDS):
-    raise NotImplementedError(
-        "source_code %r codes at most %d symbols and the vector codebook has "
-        "kmax = %d slots: cut a fit that ended at k <= %d down with "
-        "trim_vector_codebook" % (source_code, VQ_MAX_CODEWORDS,
-                                  _slots(vec_codebook), VQ_MAX_CODEWORDS))
-
-
-# the source code of compute_RD_point_mixed, Mod2 and Mod3 alone: the scalar
-# columns under the range coder, the vector index under the split range coder
-# of include/ext/vtc_index_ans_split.h, which takes up to 131 072 symbols
-_SPLIT_CODE = 'ans_split'
-
-
-def _check_mixed_source_code(source_code, from_stream):
-  if source_code == _SPLIT_CODE:
-    return
-  _scalar._check_source_code(source_code)
-  _scalar._check_from_stream(from_stream, source_code)
-
-
 # ------------------------------------------------------------- rate-distortion
 def _cluster(cluster, s, name):
   cluster = [int(c) for c in cluster]
@@ -382,6 +363,58 @@ def _cluster(cluster, s, name):
   if min(cluster) < 0 or max(cluster) >= s:
     raise ValueError('%s falls outside [0, %d)' % (name, s))
   return cluster
+
+
+def _clusters(scal_clusts, vec_clust, s):
+  """The scalar and the vector columns as lists of ints: inside [0, s), not
+  overlapping."""
+  scal = _cluster(scal_clusts, s, 'scal_clusts')
+  vec = _cluster(vec_clust, s, 'vec_clust')
+  if len(set(scal + vec)) != len(scal) + len(vec):
+    raise ValueError('scal_clusts and vec_clust overlap')
+  return scal, vec
+
+
+def _scatter(s, *parts):
+  """The (b, s) float32 codes that hold every part = (columns, dequantised
+  values (b, len(columns))), a coefficient in no part zero."""
+  values = parts[0][1]
+  codes = torch.zeros((values.shape[0], s), dtype=torch.float32,
+                      device=values.device)
+  for columns, values in parts:
+    codes.index_copy_(1, torch.as_tensor(columns, dtype=torch.int64,
+                                         device=codes.device), values)
+  return codes
+
+
+def _stacked_frequencies(scalar_freq, vector_freq):
+  """The uint16 (len(scal_clusts) + 1, kmax) frequencies of the combined index
+  array: the scalar rows, then the vector row, padded with zeros (absent
+  symbols) to the larger kmax."""
+  scalar_freq = np.asarray(scalar_freq)
+  vector_freq = np.asarray(vector_freq).reshape(1, -1)
+  if scalar_freq.ndim != 2:
+    raise ValueError('the scalar frequencies must be (len(scal_clusts), kmax)')
+  kmax = max(scalar_freq.shape[1], vector_freq.shape[1])
+  out = np.zeros((scalar_freq.shape[0] + 1, kmax), dtype=np.uint16)
+  out[:-1, :scalar_freq.shape[1]] = scalar_freq
+  out[-1, :vector_freq.shape[1]] = vector_freq[0]
+  return out
+
+
+# What a mixed point codes under each source code: the coder of the scalar
+# columns, the coder of the vector column and, where both go into ONE stream
+# set over the (b, len(scal_clusts) + 1) array [scalar columns ..., vector
+# column], how the pair `tables` = (scalar tables, vector table) is joined for
+# it.  join None: a stream set each (under 'entropy': none).
+_MixedCode = _namedtuple('_MixedCode', 'scalar vector join')
+_MIXED_CODES = {
+    'entropy': _MixedCode(_coding.Entropy, _coding.Entropy, None),
+    'huffman': _MixedCode(_coding.Huffman, _coding.Huffman,
+                          lambda scalar, vector: list(scalar) + [vector]),
+    'ans': _MixedCode(_coding.Ans, _coding.Ans,
+                      _stacked_frequencies),
+    'ans_split': _MixedCode(_coding.Ans, _coding.AnsSplit, None)}
 
 
 def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
@@ -445,18 +478,24 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
   vec_max_codewords: a vec_codebook of more than 4096 slots needs it (module
   docstring), and then source_code must be 'entropy' or 'ans_split': 'huffman'
   and 'ans' raise NotImplementedError before any device work."""
-  _check_mixed_source_code(source_code, from_stream)
-  _check_table_code(source_code, vec_codebook)
+  _scalar._source_coder(source_code, from_stream, mixed=True)
+  code = _MIXED_CODES[source_code]
+  limit = code.vector.max_symbols
+  # a coder with a symbol for every index of the largest quantiser is not
+  # asked: a codebook beyond that is _device_codebook's to refuse
+  if limit < VQ_LARGE_MAX_CODEWORDS and _slots(vec_codebook) > limit:
+    raise NotImplementedError(
+        "source_code %r codes at most %d symbols and the vector codebook has "
+        "kmax = %d slots: cut a fit that ended at k <= %d down with "
+        "trim_vector_codebook" % (source_code, limit, _slots(vec_codebook),
+                                  limit))
   codes = _scalar._codes(codes)
   patches = _scalar._codes(patches, 'patches')
   if patches.shape[0] != codes.shape[0]:
     raise ValueError('one patch per row of codes')
   b, s = codes.shape
   device = codes.device
-  scal = _cluster(scal_clusts, s, 'scal_clusts')
-  vec = _cluster(vec_clust, s, 'vec_clust')
-  if len(set(scal + vec)) != len(scal) + len(vec):
-    raise ValueError('scal_clusts and vec_clust overlap')
+  scal, vec = _clusters(scal_clusts, vec_clust, s)
   scal_at = torch.tensor(scal, dtype=torch.int64, device=device)
   vec_at = torch.tensor(vec, dtype=torch.int64, device=device)
 
@@ -474,109 +513,64 @@ def compute_RD_point_mixed(codes, patches, dictionary, scal_clusts,
       codes.index_select(1, vec_at).contiguous(), (vec_values, vec_k),
       vec_lengths, vec_lagrange_mult, True, vec_max_codewords)
 
-  dequantized = torch.zeros((b, s), dtype=torch.float32, device=device)
-  dequantized.index_copy_(1, scal_at, scal_deq)
-  dequantized.index_copy_(1, vec_at, vec_deq)
+  dequantized = _scatter(s, (scal_at, scal_deq), (vec_at, vec_deq))
   if not from_stream:
     reconstruction = _scalar._reconstruct(dequantized, dictionary)
   if int(scal_status) != 0 or int(vec_status) != 0:
     raise ValueError('compute_RD_point_mixed: the codes hold NaN')
-  if source_code == 'huffman':
-    from utils import index_coding
-    if tables is None:
-      tables = (
-          index_coding.index_huffman_tables(
-              index_counts(scal_indices, scal_pair[0].shape[1]), scal_pair[1]),
-          index_coding.index_huffman_tables(
-              vector_index_counts(vec_indices, vec_values.shape[0]),
-              vec_k)[0])
-    scalar_tables, vector_table = tables
-    streams = torch.cat([scal_indices, vec_indices[:, None]], 1)
-    all_tables = list(scalar_tables) + [vector_table]
-    if from_stream:
-      total_bits, _, (packed, offsets) = _scalar._huffman_streams(
-          streams, all_tables, None)
-      reconstruction = _scalar._reconstruct(
-          decode_codes_mixed(packed, offsets, all_tables, scal, scal_pair, vec,
-                             (vec_values, vec_k), s), dictionary)
-    else:
-      total_bits, _ = _scalar._huffman_bits(streams, all_tables, None)
-  elif source_code == 'ans':
-    from utils import index_coding
-    if tables is None:
-      tables = (
-          index_coding.index_ans_frequencies(
-              index_counts(scal_indices, scal_pair[0].shape[1]), scal_pair[1]),
-          index_coding.index_ans_frequencies(
-              vector_index_counts(vec_indices, vec_values.shape[0]),
-              vec_k)[0])
-    scalar_tables, vector_table = tables
-    streams = torch.cat([scal_indices, vec_indices[:, None]], 1)
-    all_tables = _stacked_frequencies(scalar_tables, vector_table)
-    if from_stream:
-      total_bits, _, (packed, offsets, rows) = _scalar._ans_streams(
-          streams, all_tables, None, rows_per_stream)
-      reconstruction = _scalar._reconstruct(
-          decode_codes_mixed(packed, offsets, all_tables, scal, scal_pair, vec,
-                             (vec_values, vec_k), s, ans_shape=(b, rows)),
-          dictionary)
-    else:
-      total_bits, _ = _scalar._ans_bits(streams, all_tables, None,
-                                        rows_per_stream)
-  elif source_code == _SPLIT_CODE:
-    from utils import index_coding
-    if tables is None:
-      tables = (
-          index_coding.index_ans_frequencies(
-              index_counts(scal_indices, scal_pair[0].shape[1]), scal_pair[1]),
-          index_coding.index_ans_split_frequencies(
-              vector_index_counts(vec_indices, vec_values.shape[0],
-                                  vec_max_codewords), vec_k))
-    scalar_tables, vector_table = tables
-    if from_stream:
-      scal_streams = index_coding.pack_index_ans(scal_indices, scalar_tables,
-                                                 rows_per_stream)
-      vec_streams = index_coding.pack_index_ans_split(
-          vec_indices, vector_table, rows_per_stream)
-      total_bits = 8 * (int(scal_streams[1][-1]) + int(vec_streams[1][-1]))
-      reconstruction = _scalar._reconstruct(
-          decode_codes_mixed_split(
-              scal_streams, vec_streams, tables, scal, scal_pair, vec,
-              (vec_values, vec_k), s, b, vec_max_codewords), dictionary)
-    else:
-      total_bits = 8 * (
-          int(index_coding.index_ans_stream_bytes(
-              scal_indices, scalar_tables, rows_per_stream).sum()) +
-          int(index_coding.index_ans_split_stream_bytes(
-              vec_indices, vector_table, rows_per_stream).sum()))
+  scal_counts = lambda: index_counts(scal_indices, scal_pair[0].shape[1])
+  vec_counts = lambda: vector_index_counts(vec_indices, vec_values.shape[0],
+                                           vec_max_codewords)
+  if not code.scalar.has_tables:
+    total_bits = (entropy_bits(scal_counts()) +
+                  entropy_bits(vec_counts()[None, :]))
   else:
-    total_bits = (
-        entropy_bits(index_counts(scal_indices, scal_pair[0].shape[1])) +
-        entropy_bits(vector_index_counts(vec_indices, vec_values.shape[0],
-                                         vec_max_codewords)[None, :]))
+    if tables is None:
+      tables = (code.scalar.train(scal_counts(), scal_pair[1]),
+                code.vector.train_column(vec_counts(), vec_k))
+    # what is coded, as (coder, indices, tables): the scalar and the vector
+    # part, or one part over the joined index array
+    parts = [(code.scalar, scal_indices, tables[0]),
+             (code.vector, vec_indices, tables[1])]
+    if code.join is not None:
+      parts = [(code.scalar, torch.cat([scal_indices, vec_indices[:, None]], 1),
+                code.join(*tables))]
+    if from_stream:
+      parts = [(coder, coder.pack(indices, part_tables, rows_per_stream),
+                part_tables) for coder, indices, part_tables in parts]
+      total_bits = sum(streams.bits for _, streams, _ in parts)
+      reconstruction = _scalar._reconstruct(
+          _decode_mixed(parts, scal_at, scal_pair, vec_at,
+                        (vec_values, vec_k), s, vec_max_codewords), dictionary)
+    else:
+      total_bits = sum(
+          coder.total_bits(indices, part_tables, rows_per_stream)
+          for coder, indices, part_tables in parts)
   rate = total_bits / float(patches.numel())
   distortion = _scalar._distortion(patches, reconstruction,
                                    fullimg_reshape_params)
-  if source_code == 'huffman':
-    return rate, distortion, (list(scalar_tables), vector_table)
-  if source_code in ('ans', _SPLIT_CODE):
-    return rate, distortion, (scalar_tables, vector_table)
+  if code.scalar.has_tables:
+    return rate, distortion, tuple(tables)
   return rate, distortion
 
 
-def _stacked_frequencies(scalar_freq, vector_freq):
-  """The uint16 (len(scal_clusts) + 1, kmax) frequencies of the combined index
-  array: the scalar rows, then the vector row, padded with zeros (absent
-  symbols) to the larger kmax."""
-  scalar_freq = np.asarray(scalar_freq)
-  vector_freq = np.asarray(vector_freq).reshape(1, -1)
-  if scalar_freq.ndim != 2:
-    raise ValueError('the scalar frequencies must be (len(scal_clusts), kmax)')
-  kmax = max(scalar_freq.shape[1], vector_freq.shape[1])
-  out = np.zeros((scalar_freq.shape[0] + 1, kmax), dtype=np.uint16)
-  out[:-1, :scalar_freq.shape[1]] = scalar_freq
-  out[-1, :vector_freq.shape[1]] = vector_freq[0]
-  return out
+def _decode_mixed(parts, scal, scal_codebooks, vec, vec_codebook, s,
+                  vec_max_codewords=VQ_MAX_CODEWORDS):
+  """The (b, s) dequantised codes of the stream sets in parts = [(coder,
+  stream set, tables)], one part for the joined index array or the scalar and
+  the vector part: unpack, quantization.dequantize_assignments into the
+  columns `scal`, vector_dequantize into the columns `vec`."""
+  indices = [coder.unpack(streams, tables) for coder, streams, tables in parts]
+  if len(indices) == 1:
+    scal_indices = indices[0][:, :len(scal)].contiguous()
+    vec_indices = indices[0][:, len(scal)].contiguous()
+  else:
+    scal_indices, vec_indices = indices
+  scal_deq = _scalar.dequantize_assignments(scal_indices, scal_codebooks)
+  vec_deq = vector_dequantize(vec_indices, vec_codebook, vec_max_codewords)
+  if vec_deq.shape[1] != len(vec):
+    raise ValueError('vec_codebook must be (kmax, %d)' % len(vec))
+  return _scatter(s, (scal, scal_deq), (vec, vec_deq))
 
 
 def decode_codes_mixed(packed, offsets, tables, scal_clusts, scal_codebooks,
@@ -594,29 +588,15 @@ def decode_codes_mixed(packed, offsets, tables, scal_clusts, scal_codebooks,
   index_coding.pack_index_ans, `tables` the uint16 (len(scal_clusts) + 1,
   kmax) frequencies in that order, read by index_coding.unpack_index_ans."""
   s = int(s)
-  scal = _cluster(scal_clusts, s, 'scal_clusts')
-  vec = _cluster(vec_clust, s, 'vec_clust')
-  if len(set(scal + vec)) != len(scal) + len(vec):
-    raise ValueError('scal_clusts and vec_clust overlap')
-  if ans_shape is None:
+  scal, vec = _clusters(scal_clusts, vec_clust, s)
+  coder, streams = _scalar._stream_set(packed, offsets, ans_shape)
+  if coder is _coding.Huffman:
     tables = list(tables)
   if len(tables) != len(scal) + 1:
     raise ValueError('%d tables for %d scalar columns and the vector column'
                      % (len(tables), len(scal)))
-  indices = _scalar._unpack_indices(packed, offsets, tables, ans_shape)
-  device = indices.device
-  scal_deq = _scalar.dequantize_assignments(
-      indices[:, :len(scal)].contiguous(), scal_codebooks)
-  vec_deq = vector_dequantize(indices[:, len(scal)].contiguous(), vec_codebook)
-  if vec_deq.shape[1] != len(vec):
-    raise ValueError('vec_codebook must be (kmax, %d)' % len(vec))
-  codes = torch.zeros((indices.shape[0], s), dtype=torch.float32,
-                      device=device)
-  codes.index_copy_(1, torch.tensor(scal, dtype=torch.int64, device=device),
-                    scal_deq)
-  codes.index_copy_(1, torch.tensor(vec, dtype=torch.int64, device=device),
-                    vec_deq)
-  return codes
+  return _decode_mixed([(coder, streams, tables)], scal, scal_codebooks, vec,
+                       vec_codebook, s)
 
 
 def decode_codes_mixed_split(scalar_streams, vector_streams, tables,
@@ -633,33 +613,19 @@ def decode_codes_mixed_split(scalar_streams, vector_streams, tables,
   vector_dequantize (with vec_max_codewords) into the columns vec_clust; a
   column in neither cluster is zero.  Two host reads (the decoders'
   statuses)."""
-  from utils import index_coding
   s, b = int(s), int(b)
-  scal = _cluster(scal_clusts, s, 'scal_clusts')
-  vec = _cluster(vec_clust, s, 'vec_clust')
-  if len(set(scal + vec)) != len(scal) + len(vec):
-    raise ValueError('scal_clusts and vec_clust overlap')
+  scal, vec = _clusters(scal_clusts, vec_clust, s)
   scalar_tables, vector_table = tables
   if len(scalar_tables) != len(scal):
     raise ValueError('%d rows of frequencies for %d scalar columns'
                      % (len(scalar_tables), len(scal)))
-  scal_indices = index_coding.unpack_index_ans(
-      scalar_streams[0], scalar_streams[1], scalar_tables, b,
-      scalar_streams[2])
-  vec_indices = index_coding.unpack_index_ans_split(
-      vector_streams[0], vector_streams[1], vector_table, b,
-      vector_streams[2])
-  device = scal_indices.device
-  scal_deq = _scalar.dequantize_assignments(scal_indices, scal_codebooks)
-  vec_deq = vector_dequantize(vec_indices, vec_codebook, vec_max_codewords)
-  if vec_deq.shape[1] != len(vec):
-    raise ValueError('vec_codebook must be (kmax, %d)' % len(vec))
-  codes = torch.zeros((b, s), dtype=torch.float32, device=device)
-  codes.index_copy_(1, torch.tensor(scal, dtype=torch.int64, device=device),
-                    scal_deq)
-  codes.index_copy_(1, torch.tensor(vec, dtype=torch.int64, device=device),
-                    vec_deq)
-  return codes
+  code = _MIXED_CODES['ans_split']
+  stream_set = lambda streams: _coding.StreamSet(streams[0], streams[1], b,
+                                                 streams[2], None)
+  return _decode_mixed(
+      [(code.scalar, stream_set(scalar_streams), scalar_tables),
+       (code.vector, stream_set(vector_streams), vector_table)],
+      scal, scal_codebooks, vec, vec_codebook, s, vec_max_codewords)
 
 
 def _gathered(codes, cluster):
@@ -679,8 +645,8 @@ def _fit_vector_part(codes, vec_clust, vec_quant_multiplier, vec_init_num_bins,
       initial_vector_codebook(vectors, vec_init_num_bins, max_codewords),
       lagrange_mult=vec_quant_multiplier, max_iterations=max_iterations,
       epsilon=epsilon, max_codewords=max_codewords)
-  if (source_code in _scalar._TABLE_CODES and
-      _slots(fitted) > VQ_MAX_CODEWORDS):
+  code = _MIXED_CODES.get(source_code)   # _mixed_point refuses other names
+  if code and _slots(fitted) > code.vector.max_symbols:
     fitted = trim_vector_codebook(fitted)
   return fitted, fitted['lengths']
 
@@ -689,17 +655,12 @@ def _mixed_point(who, training, source_code, from_stream, rows_per_stream,
                  huff_tab1, huff_tab2, *args, **kwargs):
   """compute_RD_point_mixed for Mod2 / Mod3: (rate, distortion, huff_tab1,
   huff_tab2), the two tables None under 'entropy'."""
-  _check_mixed_source_code(source_code, from_stream)
-  if source_code not in _scalar._TABLE_CODES + (_SPLIT_CODE,):
+  coder = _scalar._source_coder(source_code, from_stream, mixed=True)
+  if not coder.has_tables:
     return compute_RD_point_mixed(*args, **kwargs) + (None, None)
   tables = None
   if not training:
-    if source_code != _SPLIT_CODE:
-      _scalar._need_tables(who, huff_tab1, huff_tab2, source_code=source_code)
-    elif huff_tab1 is None or huff_tab2 is None:
-      raise ValueError("%s: source_code='ans_split' with precomputed "
-                       'codebooks needs the frequencies of the training call '
-                       'as well' % who)
+    _scalar._need_tables(who, coder, huff_tab1, huff_tab2)
     tables = (huff_tab1, huff_tab2)
   rate, distortion, tables = compute_RD_point_mixed(
       *args, source_code=source_code, tables=tables, from_stream=from_stream,
