@@ -55,6 +55,16 @@
 // (profiles/fused_mfma_shape.txt).  default_tile16() picks per precision,
 // VTC_FUSED_TILE=32|16 forces one.  The two differ in the last bits of the
 // codes only: one MFMA accumulates over K = 32 instead of 16.
+//
+// Schedules.  fused_fista_kernel16 has three schedule bits (comment there;
+// VTC_FUSED_SCHED=0..7 forces one, default_sched() picks per precision), none
+// of which changes an operand, a product or a summation order: the epilogue of
+// the middle phases spread over two segments, the residual exchange started
+// under the iteration's last step 3, and the residual operands of step 1's
+// first k-steps kept in registers for the NPH phases of an iteration instead
+// of being read from LDS in each (profiles/fused_resident_operand.txt).  That
+// kernel also has the variant (FISTA / ISTA) compiled in; the 32x32x16 kernel
+// has one schedule and selects the variant at run time.
 #include "fc_fused.h"
 #include "fused_common.h"
 
@@ -696,13 +706,61 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel(FusedParams P) {
 //   bit 1: the iteration's last step 3 walks its fragments pixel-block-major
 //          (blocks {0, 1} over the four k-steps, then {2, 3}), and the residual
 //          exchange of blocks 0 and 1 runs in the MFMA gaps of the second half.
+//   bit 2: the B operands of step 1's first kResidentKsteps k-steps (the
+//          residual R_k: the same in all NPH phases of an iteration) are read
+//          from the exchange image once per iteration and kept in registers;
+//          the other k-steps keep their one-ahead ds_read_b128.
+// FISTA compiles the variant in: the 32x32x16 kernel selects at run time.
+//
+// split_group: split_packed<F16, 4> with the lo part's subtraction written per
+// element.  split_operand.h subtracts a pair at a time, which becomes
+// v_pk_add_f32: 49 of them per iteration of the f16x3 kernel, each of which
+// costs about three plain f32 instructions beside MFMAs
+// (MI355X_MICROARCH.md).  Same conversions, same subtraction, same bits.
+template <bool F16, bool LO>
+__device__ __forceinline__ void split_group(const float (&v)[4], uint2& hi_out,
+                                            uint2& lo_out) {
+  if constexpr (F16) {
+    typedef float pair_f32 __attribute__((ext_vector_type(2)));
+    typedef _Float16 pair_f16 __attribute__((ext_vector_type(2)));
+    unsigned hw[2], lw[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const pair_f32 x = {v[2 * k], v[2 * k + 1]};
+      const pair_f16 h = __builtin_convertvector(x, pair_f16);
+      hw[k] = __builtin_bit_cast(unsigned, h);
+      if (LO) {
+        const float d0 = sub_rn(v[2 * k], (float)h[0]);
+        const float d1 = sub_rn(v[2 * k + 1], (float)h[1]);
+        const pair_f32 d = {d0, d1};
+        lw[k] = __builtin_bit_cast(unsigned,
+                                   __builtin_convertvector(d, pair_f16));
+      }
+    }
+    hi_out = make_uint2(hw[0], hw[1]);
+    if (LO) lo_out = make_uint2(lw[0], lw[1]);
+  } else {
+    split_packed<F16, 4, LO>(v, hi_out, lo_out);
+  }
+}
+// kResidentKsteps: 2, 3 and 4 were built (-DVTC_FUSED_KRES) and measured, all
+// without scratch; each step is faster than the one before it, 4 is what
+// schedule 7 of f16x3 still holds in its 512 registers
+// (profiles/fused_resident_operand.txt).
+#ifndef VTC_FUSED_KRES
+#define VTC_FUSED_KRES 4
+#endif
+constexpr int kResidentKsteps = VTC_FUSED_KRES;
 template <int NPH, int NP, int MODE, bool F16 = false, bool STAMP = false,
-          int SCHED = 0>
+          int SCHED = 0, bool FISTA = true>
 __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   static_assert(!F16 || NP == 2, "the f16 split exists as three products only");
-  static_assert(SCHED >= 0 && SCHED < 4, "two schedule bits");
+  static_assert(SCHED >= 0 && SCHED < 8, "three schedule bits");
   constexpr bool SPREAD = (SCHED & 1) != 0 && NPH > 2;
   constexpr bool EARLY_R = (SCHED & 2) != 0;
+  constexpr int KRES = (SCHED & 4) != 0 ? kResidentKsteps : 0;
+  constexpr int KR = KRES > 0 ? KRES : 1;
+  static_assert(KRES >= 0 && KRES < 8, "step 1 has eight k-steps");
   using L = FusedLds<NPH, NP>;
   constexpr int CREG = L::CREG;
   constexpr int CR = CREG > 0 ? CREG : 1;
@@ -766,6 +824,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   f32x4 Xr[4][2];     // [16-pixel block][patch half]: pixel 16nb + 4q + k
   f32x4 Racc[4][2];
   uint4 ring[NP][RING];
+  uint4 rres[KR][2][NP];   // KRES: B operands of step 1's first k-steps
 
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
@@ -901,7 +960,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   auto publish_group = [&](const f32x16& y, int g, int buf) {
     const float v4[4] = {y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3]};
     uint2 hi, lo;
-    split_packed<F16, 4, NP == 2>(v4, hi, lo);
+    split_group<F16, NP == 2>(v4, hi, lo);
     char* dst = Yx + buf * NP * kYxPart + yx_wr + 32 * (g >> 1) +
                 kYxHalf * (g & 1);
     *reinterpret_cast<uint2*>(dst) = hi;
@@ -1055,7 +1114,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
       for (int n = 0; n < 2; ++n) {
         const float v4[4] = {v[nb][n][0], v[nb][n][1], v[nb][n][2], v[nb][n][3]};
         uint2 hi, lo;
-        split_packed<F16, 4, NP == 2>(v4, hi, lo);
+        split_group<F16, NP == 2>(v4, hi, lo);
         char* dst = Rx + rx_wr + 32 * nb + kRxHalf * n;
         *reinterpret_cast<uint2*>(dst) = hi;
         if (NP == 2) *reinterpret_cast<uint2*>(dst + kRxPart) = lo;
@@ -1108,7 +1167,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   };
   auto exchange_block_b = [&](int nb, int n) {
     uint2 hi, lo;
-    split_packed<F16, 4, NP == 2>(xv, hi, lo);
+    split_group<F16, NP == 2>(xv, hi, lo);
     char* dst = Rx + rx_wr + 32 * nb + kRxHalf * n;
     *reinterpret_cast<uint2*>(dst) = hi;
     if (NP == 2) *reinterpret_cast<uint2*>(dst + kRxPart) = lo;
@@ -1233,7 +1292,7 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
     for (int part = 0; part < NP; ++part)
       ring[part][i] = VTC_LOAD_SEG(part, 0, i);
 
-  const bool fista = P.fista != 0;   // ISTA: every beta is 0
+  // (the variant is compiled in: ISTA has no momentum arithmetic, FISTA no select)
   unsigned long long acc_t[5] = {0, 0, 0, 0, 0};
   unsigned long long t0 = 0, t1 = 0;
 #define VTC_STAMP(slot)                    \
@@ -1282,7 +1341,12 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
                    : (k == 2) ? cold4.z : cold4.w;
     const float cv = sub_rn(Y[p][e], mul_rn(eta, Gp[g][k]));
     const float cn = shrink_fast<MODE>(cv, cutoff_l[g & 1]);
-    Y[p][e] = fista ? add_rn(cn, mul_rn(beta, sub_rn(cn, co))) : cn;
+    // ISTA: y = codes (ista_fista.py:133), not codes + 0 * (codes - old):
+    // a code that has overflowed to inf stays inf as it does there
+    if constexpr (FISTA)
+      Y[p][e] = add_rn(cn, mul_rn(beta, sub_rn(cn, co)));
+    else
+      Y[p][e] = cn;
     cn4[k] = cn;
     if (k == 3) {
       if (p < CREG) {
@@ -1328,7 +1392,10 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
     } else {
       const float co = (k == 0) ? cold4.x : (k == 1) ? cold4.y
                      : (k == 2) ? cold4.z : cold4.w;
-      Y[p][e] = fista ? add_rn(cn, mul_rn(beta, sub_rn(cn, co))) : cn;
+      if constexpr (FISTA)
+        Y[p][e] = add_rn(cn, mul_rn(beta, sub_rn(cn, co)));
+      else
+        Y[p][e] = cn;
     }
     if (k == 3) {
       if (p < CREG) {
@@ -1364,12 +1431,14 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) G[g][k] = 0.f;
     uint4 rb[2][NP], rb_next[2][NP];
+    if constexpr (KRES == 0) {
 #pragma unroll
-    for (int n = 0; n < 2; ++n)
+      for (int n = 0; n < 2; ++n)
 #pragma unroll
-      for (int part = 0; part < NP; ++part)
-        rb_next[n][part] = *reinterpret_cast<const uint4*>(
-            Rx + part * kRxPart + rx_rd + kRxHalf * n);
+        for (int part = 0; part < NP; ++part)
+          rb_next[n][part] = *reinterpret_cast<const uint4*>(
+              Rx + part * kRxPart + rx_rd + kRxHalf * n);
+    }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int ks = i >> 1, m = i & 1;
@@ -1377,9 +1446,13 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
 #pragma unroll
         for (int n = 0; n < 2; ++n)
 #pragma unroll
-          for (int part = 0; part < NP; ++part) rb[n][part] = rb_next[n][part];
+          for (int part = 0; part < NP; ++part)
+            rb[n][part] = ks < KRES ? rres[ks < KRES ? ks : 0][n][part]
+                                    : rb_next[n][part];
       }
-      if (ks + 1 < 8) {
+      // (the resident k-steps need no fetch: the first one under way is that
+      // of k-step KRES, under the positions of k-step KRES - 1)
+      if (ks + 1 < 8 && ks + 1 >= KRES) {
 #pragma unroll
         for (int part = 0; part < NP; ++part)
           rb_next[m][part] = *reinterpret_cast<const uint4*>(
@@ -1402,7 +1475,21 @@ __global__ __launch_bounds__(256, 1) void fused_fista_kernel16(FusedParams P) {
   };
 
   for (int it = 0; it < P.num_iters; ++it) {
-    const float beta = fista ? P.betas[it] : 0.f;
+    float beta = 0.f;
+    if constexpr (FISTA) beta = P.betas[it];
+    // KRES: R_k is final and visible (the exchange's closing barrier is behind
+    // us, the range guard's factor already in the published parts) and does
+    // not change until this iteration's exchange, which follows every step 1
+    if constexpr (KRES > 0) {
+#pragma unroll
+      for (int ks = 0; ks < KRES; ++ks)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int part = 0; part < NP; ++part)
+            rres[ks][n][part] = *reinterpret_cast<const uint4*>(
+                Rx + part * kRxPart + rx_rd + kRxHalf * n + 64 * ks);
+    }
     step1(0, 0, 0, beta);
     VTC_STAMP(0)
 #pragma unroll
@@ -1543,39 +1630,44 @@ static bool use_tile16(int precision) {
 }
 
 // Which schedule the 16x16x32 kernel runs by default: the spread epilogue for
-// f16x3 and bf16 (0.9 % and 2.8 % faster per step at the benchmark shape);
-// the early exchange is no gain and stays off, bf16x3 on this tile is a forced
-// arm and was not measured (profiles/fused_epilogue_spread.txt).
+// f16x3 and bf16 (0.9 % and 2.8 % faster per step at the benchmark shape,
+// profiles/fused_epilogue_spread.txt) with the resident residual operand
+// (another 1.1 % and 1.1 %, profiles/fused_resident_operand.txt); the early
+// exchange is no gain and stays off, bf16x3 on this tile is a forced arm and
+// was not measured.
 template <int NP, bool F16>
 constexpr int default_sched() {
-  return (F16 || NP == 1) ? 1 : 0;
+  return (F16 || NP == 1) ? (1 | 4) : 0;
 }
-// VTC_FUSED_SCHED=0|1|2|3 forces a schedule: bit 0 spreads the epilogue of the
+// VTC_FUSED_SCHED=0..7 forces a schedule: bit 0 spreads the epilogue of the
 // middle phases, bit 1 starts the residual exchange under the iteration's last
-// step 3 (a diagnostic switch, read on every call, as VTC_FUSED_TILE is).  The
-// 32x32x16 kernel has one schedule.
+// step 3, bit 2 keeps step 1's first residual operands in registers (a
+// diagnostic switch, read on every call, as VTC_FUSED_TILE is).  The 32x32x16
+// kernel has one schedule.
 static int use_sched(int by_default) {
   const char* v = getenv("VTC_FUSED_SCHED");
-  if (v && v[0] >= '0' && v[0] <= '3' && v[1] == 0) return v[0] - '0';
+  if (v && v[0] >= '0' && v[0] <= '7' && v[1] == 0) return v[0] - '0';
   return by_default;
 }
 
+// FISTA: the variant of the 16x16x32 kernel; the 32x32x16 kernel reads
+// P.fista and has the one instantiation (FISTA = true here).
 template <int NPH, int NP, int MODE, bool F16, bool STAMP, bool TILE16,
-          int SCHED>
+          int SCHED, bool FISTA>
 static auto fused_kernel() {
-  static_assert(TILE16 || SCHED == 0, "schedules exist on the 16x16x32 tile");
-  if constexpr (TILE16 && SCHED != 0)
-    return fused_fista_kernel16<NPH, NP, MODE, F16, STAMP, SCHED>;
-  else if constexpr (TILE16)
-    return fused_fista_kernel16<NPH, NP, MODE, F16, STAMP>;
+  static_assert(TILE16 || (SCHED == 0 && FISTA),
+                "schedules and variants exist on the 16x16x32 tile");
+  if constexpr (TILE16)
+    return fused_fista_kernel16<NPH, NP, MODE, F16, STAMP, SCHED, FISTA>;
   else
     return fused_fista_kernel<NPH, NP, MODE, F16, STAMP>;
 }
 
-template <int NPH, int NP, int MODE, bool F16, bool TILE16, int SCHED>
+template <int NPH, int NP, int MODE, bool F16, bool TILE16, int SCHED,
+          bool FISTA>
 static int launch_fused(const FusedParams& P, hipStream_t st) {
   using L = FusedLds<NPH, NP>;
-  auto kernel = fused_kernel<NPH, NP, MODE, F16, false, TILE16, SCHED>();
+  auto kernel = fused_kernel<NPH, NP, MODE, F16, false, TILE16, SCHED, FISTA>();
   static unsigned long long configured = 0;
   if (first_use_on_this_device(&configured)) {
     VTC_HIP_CHECK(hipFuncSetAttribute(
@@ -1589,16 +1681,16 @@ static int launch_fused(const FusedParams& P, hipStream_t st) {
 }
 
 // Diagnostic: VTC_FUSED_STAMPS=1 runs the stamped instantiation (soft
-// threshold only) and prints per-segment cycle shares.  Its run time is not
-// representative (the stamps fence the schedule); read the shares only.
+// threshold, FISTA only) and prints per-segment cycle shares.  Its run time is
+// not representative (the stamps fence the schedule); read the shares only.
 template <int NPH, int NP, bool F16, bool TILE16, int SCHED>
 static int launch_stamped(FusedParams P, hipStream_t st) {
   using L = FusedLds<NPH, NP>;
   static const bool no_epilogue = getenv("VTC_FUSED_NOEPI") != nullptr;
   auto kernel =
       no_epilogue
-          ? fused_kernel<NPH, NP, 7, F16, true, TILE16, SCHED>()
-          : fused_kernel<NPH, NP, VTC_SOFT, F16, true, TILE16, SCHED>();
+          ? fused_kernel<NPH, NP, 7, F16, true, TILE16, SCHED, true>()
+          : fused_kernel<NPH, NP, VTC_SOFT, F16, true, TILE16, SCHED, true>();
   unsigned long long* dev = nullptr;
   VTC_HIP_CHECK(hipMalloc(&dev, 8 * sizeof(unsigned long long)));
   VTC_HIP_CHECK(hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), st));
@@ -1625,25 +1717,40 @@ static int launch_stamped(FusedParams P, hipStream_t st) {
   return VTC_OK;
 }
 
+template <int NPH, int NP, bool F16, bool TILE16, int SCHED, bool FISTA>
+static int dispatch_threshold(const FusedParams& P, int threshold,
+                              hipStream_t st) {
+  switch (threshold) {
+    case VTC_SOFT:
+      return launch_fused<NPH, NP, VTC_SOFT, F16, TILE16, SCHED, FISTA>(P, st);
+    case VTC_SOFT_NONNEG:
+      return launch_fused<NPH, NP, VTC_SOFT_NONNEG, F16, TILE16, SCHED, FISTA>(
+          P, st);
+    case VTC_HARD:
+      return launch_fused<NPH, NP, VTC_HARD, F16, TILE16, SCHED, FISTA>(P, st);
+    default:
+      return launch_fused<NPH, NP, VTC_HARD_NONNEG, F16, TILE16, SCHED, FISTA>(
+          P, st);
+  }
+}
+
 template <int NPH, int NP, bool F16, bool TILE16, int SCHED>
 static int dispatch_mode(const FusedParams& P, int threshold, hipStream_t st) {
   static const bool stamps = getenv("VTC_FUSED_STAMPS") != nullptr;
   // the stamped run is of the benchmark's shape; schedule 0 keeps the
   // instantiations it always had
   if constexpr (SCHED == 0 || (NPH == 8 && NP == 2)) {
-    if (stamps && threshold == VTC_SOFT && NPH == 8 && NP == 2)
+    if (stamps && threshold == VTC_SOFT && NPH == 8 && NP == 2 &&
+        (P.fista || !TILE16))
       return launch_stamped<NPH, NP, F16, TILE16, SCHED>(P, st);
   }
-  switch (threshold) {
-    case VTC_SOFT:
-      return launch_fused<NPH, NP, VTC_SOFT, F16, TILE16, SCHED>(P, st);
-    case VTC_SOFT_NONNEG:
-      return launch_fused<NPH, NP, VTC_SOFT_NONNEG, F16, TILE16, SCHED>(P, st);
-    case VTC_HARD:
-      return launch_fused<NPH, NP, VTC_HARD, F16, TILE16, SCHED>(P, st);
-    default:
-      return launch_fused<NPH, NP, VTC_HARD_NONNEG, F16, TILE16, SCHED>(P, st);
+  if constexpr (TILE16) {
+    if (!P.fista)
+      return dispatch_threshold<NPH, NP, F16, TILE16, SCHED, false>(
+          P, threshold, st);
   }
+  return dispatch_threshold<NPH, NP, F16, TILE16, SCHED, true>(P, threshold,
+                                                               st);
 }
 
 // The schedule of a call: one on the 32x32x16 tile; on the other the switch's
@@ -1652,15 +1759,21 @@ template <int NPH, int NP, bool F16, bool TILE16>
 static int dispatch_sched(const FusedParams& P, int threshold,
                           hipStream_t st) {
   if constexpr (TILE16) {
-    const int sched = use_sched(default_sched<NP, F16>());
+    int sched = use_sched(default_sched<NP, F16>());
+    if (NPH == 2) sched &= ~1;
     if constexpr (NPH > 2) {
-      if (sched == 1)
-        return dispatch_mode<NPH, NP, F16, TILE16, 1>(P, threshold, st);
-      if (sched == 3)
-        return dispatch_mode<NPH, NP, F16, TILE16, 3>(P, threshold, st);
+      switch (sched) {
+        case 1: return dispatch_mode<NPH, NP, F16, TILE16, 1>(P, threshold, st);
+        case 3: return dispatch_mode<NPH, NP, F16, TILE16, 3>(P, threshold, st);
+        case 5: return dispatch_mode<NPH, NP, F16, TILE16, 5>(P, threshold, st);
+        case 7: return dispatch_mode<NPH, NP, F16, TILE16, 7>(P, threshold, st);
+      }
     }
-    if (sched & 2)
-      return dispatch_mode<NPH, NP, F16, TILE16, 2>(P, threshold, st);
+    switch (sched) {
+      case 2: return dispatch_mode<NPH, NP, F16, TILE16, 2>(P, threshold, st);
+      case 4: return dispatch_mode<NPH, NP, F16, TILE16, 4>(P, threshold, st);
+      case 6: return dispatch_mode<NPH, NP, F16, TILE16, 6>(P, threshold, st);
+    }
   }
   return dispatch_mode<NPH, NP, F16, TILE16, 0>(P, threshold, st);
 }
