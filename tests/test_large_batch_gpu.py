@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_routes_data as crd
 import helpers
 import sc_oracle
 
@@ -120,24 +121,12 @@ def test_fully_connected_route(device, fc, case):
 
 
 def _conv_route(geom):
-  """Which exact-f32 route vtc_conv_ista_fista takes for a geometry
-  (csrc/conv.hip, the dispatch of the iteration loop), mirroring
-  patch_geometry (csrc/conv_patch.h) and unit_geometry / unit_analysis_fits
-  (csrc/conv_unit.h)."""
-  ceil = lambda a, b: -(-a // b)
-  ch = (geom.h - geom.kh) // geom.stride_v + 1
-  cw = (geom.w - geom.kw) // geom.stride_h + 1
-  cover = ceil(geom.kh, geom.stride_v) * ceil(geom.kw, geom.stride_h)
-  if ((geom.stride_v > 1 or geom.stride_h > 1) and cover <= 16 and
-      geom.c * geom.kh * geom.kw <= 8192 and geom.b <= 65535 and
-      geom.b * ch * cw < (1 << 31)):
-    return 'patch'
-  unit = (geom.stride_v == 1 and geom.stride_h == 1 and geom.kh == geom.kw and
-          geom.kh in (5, 8, 11, 16))
-  wy, wx = 32 + geom.kh - 1, (64 + geom.kw - 1 + 3) // 4 * 4
-  fits = (geom.c * wy * wx + geom.s * geom.c * geom.kh *
-          ((geom.kw + 3) // 4 * 4)) * 4 <= 140 * 1024
-  return 'unit' if unit and fits else 'direct'
+  """Which exact-f32 route vtc_conv_ista_fista takes for a geometry: the
+  family of the dispatch mirror in tests/conv_routes_data.py (patch, unit,
+  or direct -- the direct analysis behind either synthesis)."""
+  family = crd.conv_route(geom, 'f32', torch.cuda.get_device_properties(
+      0).multi_processor_count)[0]
+  return 'direct' if family == 'unit-synth+direct' else family
 
 
 # (name, stride, kernel size, kernels, image size, images, precision passed,
