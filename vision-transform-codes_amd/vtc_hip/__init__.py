@@ -401,6 +401,30 @@ COLOR_BINDINGS = {
                                   _i32, _i32, _i32, _vp]),
 }
 
+JFIF_ABI_VERSION = 1    # VTC_JFIF_ABI_VERSION
+JFIF_STUFF_TILE = 2048  # VTC_JFIF_STUFF_TILE
+
+# The fifteenth header, include/ext/vtc_jfif.h (same library): the device half
+# of a baseline JFIF writer -- plane to quantiser levels and back, the T.81
+# symbols with DC prediction, one entropy-coded segment, byte stuffing.  Under
+# include/ext/ and named ..._BINDINGS for the reason given above.
+JFIF_BINDINGS = {
+    'vtc_jfif_abi_version': (_i32, []),
+    'vtc_jfif_forward_dct': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp,
+                                    _vp, _vp, _i64, _vp]),
+    'vtc_jfif_inverse_dct': (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp,
+                                    _i32, _i32, _vp]),
+    'vtc_jfif_symbol_counts': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
+    'vtc_jfif_block_bits': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
+    'vtc_jfif_pack': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _sz, _vp, _vp]),
+    'vtc_jfif_stuff_bytes_workspace_bytes': (_sz, [_i64]),
+    'vtc_jfif_stuff_bytes': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz,
+                                    _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -422,7 +446,7 @@ def load_library():
                 QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
                 INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES,
                 VQ_LARGE_SIGNATURES, INDEX_ANS_SPLIT_BINDINGS,
-                COLOR_BINDINGS):
+                COLOR_BINDINGS, JFIF_BINDINGS):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -456,6 +480,8 @@ def load_library():
     raise ImportError('libvtc_hip.so split index ANS ABI version mismatch')
   if lib.vtc_color_abi_version() != COLOR_ABI_VERSION:
     raise ImportError('libvtc_hip.so colour ABI version mismatch')
+  if lib.vtc_jfif_abi_version() != JFIF_ABI_VERSION:
+    raise ImportError('libvtc_hip.so JFIF ABI version mismatch')
   _lib = lib
   return lib
 
