@@ -17,12 +17,22 @@ The Huffman tables (length-limited to 16 bits by package-merge, at most 256
 symbols each) are built here on the host from the device counts, as utils.jpeg
 builds its own; so are the scan geometry and the header segments.
 
+The way back from the bytes -- decode_bytes, read_jpeg,
+rate_distortion_image(from_stream=True) -- opens one baseline file, this
+module's or another encoder's: the markers are walked here on the host
+(parse_headers, frame_layout), byte unstuffing, the self-synchronising
+parallel Huffman decode and the DC scan run in the kernels of
+csrc/jfif_decode.hip behind include/ext/vtc_jfif_decode.h, and the planes come
+from the inverse DCT above.  DESIGN.md 4.24.
+
 Planes are (h, w) float32 device tensors holding samples in [0, 255]; images
 are (h, w) or (h, w, 3) float32 device tensors.  A wrong shape raises
 ValueError, a CPU tensor VtcHipError, a level beyond the baseline sizes (10
 bits AC, 11 bits DC difference) ValueError, a symbol the tables lack KeyError
 with its spelling as in utils.jpeg.
 """
+import re
+
 import numpy as np
 import torch
 
@@ -663,11 +673,484 @@ def decode_levels(info):
                             upsampling='triangle', clamp=(0.0, 255.0))
 
 
+# ------------------------------------------------------------ reading a file
+_SOF_NAMES = {0xC1: 'extended sequential DCT (SOF1)',
+              0xC2: 'progressive DCT (SOF2)', 0xC3: 'lossless (SOF3)',
+              0xC5: 'differential sequential DCT (SOF5)',
+              0xC6: 'differential progressive DCT (SOF6)',
+              0xC7: 'differential lossless (SOF7)',
+              0xC9: 'arithmetic coding (SOF9)',
+              0xCA: 'arithmetic coding, progressive (SOF10)',
+              0xCB: 'arithmetic coding, lossless (SOF11)',
+              0xCD: 'arithmetic coding, differential (SOF13)',
+              0xCE: 'arithmetic coding, differential progressive (SOF14)',
+              0xCF: 'arithmetic coding, differential lossless (SOF15)',
+              0xCC: 'arithmetic coding (DAC)'}
+_MARKER_IN_SEGMENT = re.compile(b'\xff[^\x00]')
+
+
+def _huffman_table(counts, values, size):
+  """(lengths int64[size], codes uint16[size]) of one DHT table: codewords in
+  file order (T.81 Annex C)."""
+  lengths = np.zeros(size, dtype=np.int64)
+  codes = np.zeros(size, dtype=np.uint16)
+  code, k = 0, 0
+  for length in range(1, MAX_CODE_BITS + 1):
+    for _ in range(counts[length - 1]):
+      symbol = values[k]
+      k += 1
+      if symbol >= size:
+        raise ValueError('DHT: symbol 0x%02x in a table of %d' % (symbol, size))
+      if lengths[symbol]:
+        raise ValueError('DHT: symbol 0x%02x twice' % symbol)
+      if code >> length:
+        raise ValueError('DHT: lengths violate the Kraft inequality')
+      lengths[symbol], codes[symbol] = length, code
+      code += 1
+    code <<= 1
+  return lengths, codes
+
+
+def parse_headers(data):
+  """Walks the markers of a baseline JFIF file up to its SOS, on the host.
+
+  Returns a dict: 'shape' (h, w); 'components' [(id, H, V, Tq)] in frame
+  order; 'sampling' [(H, V)] as frame_layout takes it (a one-component file is
+  (1, 1) whatever it says: its scan is not interleaved); 'qtables' {Tq:
+  uint16[64] in zig-zag order}; 'tables', a list of two pairs {'dc': lengths
+  int64[16], 'ac': lengths int64[256], 'dc_codes', 'ac_codes': uint16
+  codewords in the file's order} as canonical_codes and _DeviceTables index
+  them (None for an id the file does not define); 'selectors' [(Td, Ta)] per
+  scan component; 'segment_at', the offset of the entropy-coded segment.
+
+  ValueError for what is not a JPEG, is truncated or refers to a missing
+  table; NotImplementedError, naming the feature, for what T.81 allows and
+  this reader leaves out."""
+  data = bytes(data)
+  if data[:2] != b'\xff\xd8':
+    raise ValueError('not a JPEG file: no SOI marker')
+  at = 2
+  qtables, frame, restart = {}, None, 0
+  huffman = {}   # (class, id) -> (lengths, codes)
+  adobe_transform = None
+  while True:
+    if at + 2 > len(data):
+      raise ValueError('truncated: the file ends before its SOS marker')
+    if data[at] != 0xFF:
+      raise ValueError('not a JPEG file: 0x%02x at offset %d where a marker '
+                       'should be' % (data[at], at))
+    marker = data[at + 1]
+    if marker == 0xFF:      # fill byte
+      at += 1
+      continue
+    if marker == 0x01 or 0xD0 <= marker <= 0xD7:
+      at += 2
+      continue
+    if marker == 0xD9:
+      raise ValueError('truncated: EOI before any scan')
+    if at + 4 > len(data):
+      raise ValueError('truncated: marker 0x%02x without a length' % marker)
+    size = int.from_bytes(data[at + 2:at + 4], 'big')
+    body = data[at + 4:at + 2 + size]
+    if size < 2 or at + 2 + size > len(data):
+      raise ValueError('truncated: segment 0x%02x of %d bytes at offset %d'
+                       % (marker, size, at))
+    at += 2 + size
+    if marker in _SOF_NAMES:
+      raise NotImplementedError(_SOF_NAMES[marker] + ': only baseline '
+                                'sequential DCT (SOF0) is read')
+    if marker == 0xDB:
+      while body:
+        if body[0] >> 4:
+          raise NotImplementedError('16-bit DQT entries')
+        if len(body) < 65:
+          raise ValueError('truncated: DQT')
+        qtables[body[0] & 15] = np.array(list(body[1:65]), dtype=np.uint16)
+        body = body[65:]
+    elif marker == 0xC0:
+      if len(body) < 6 or len(body) < 6 + 3 * body[5]:
+        raise ValueError('truncated: SOF0')
+      if body[0] != 8:
+        raise NotImplementedError('%d-bit samples' % body[0])
+      frame = {'h': int.from_bytes(body[1:3], 'big'),
+               'w': int.from_bytes(body[3:5], 'big'),
+               'components': [(body[6 + 3 * i], body[7 + 3 * i] >> 4,
+                               body[7 + 3 * i] & 15, body[8 + 3 * i])
+                              for i in range(body[5])]}
+    elif marker == 0xC4:
+      while body:
+        klass, index = body[0] >> 4, body[0] & 15
+        if len(body) < 17 or len(body) < 17 + sum(body[1:17]):
+          raise ValueError('truncated: DHT')
+        if klass > 1:
+          raise ValueError('DHT: table class %d' % klass)
+        if index > 1:
+          raise NotImplementedError('Huffman table ids above 1 (baseline '
+                                    'allows 0 and 1)')
+        counts = list(body[1:17])
+        huffman[(klass, index)] = _huffman_table(
+            counts, list(body[17:17 + sum(counts)]), 256 if klass else 16)
+        body = body[17 + sum(counts):]
+    elif marker == 0xDD:
+      if len(body) < 2:
+        raise ValueError('truncated: DRI')
+      restart = int.from_bytes(body[:2], 'big')
+    elif marker == 0xEE and body[:5] == b'Adobe' and len(body) >= 12:
+      adobe_transform = body[11]
+    elif marker == 0xDA:
+      break
+  if frame is None:
+    raise ValueError('SOS before any frame header')
+  if restart:
+    raise NotImplementedError('restart intervals (DRI %d)' % restart)
+  comps = frame['components']
+  if len(comps) not in (1, 3):
+    raise NotImplementedError('%d components: one (gray) or three (YCbCr) '
+                              'are read' % len(comps))
+  if frame['h'] < 1 or frame['w'] < 1:
+    raise ValueError('a frame of %d x %d' % (frame['h'], frame['w']))
+  if len(comps) == 3:
+    if adobe_transform == 0:
+      raise NotImplementedError('an Adobe APP14 segment that says RGB')
+    if comps[0][1] not in (1, 2) or comps[0][2] not in (1, 2):
+      raise NotImplementedError('luma sampling %d x %d: 1 or 2 each way'
+                                % (comps[0][1], comps[0][2]))
+    if [c[1:3] for c in comps[1:]] != [(1, 1), (1, 1)]:
+      raise NotImplementedError('chroma sampling other than 1 x 1')
+    sampling = [c[1:3] for c in comps]
+  else:
+    sampling = [(1, 1)]
+  if len(body) < 1 or len(body) < 4 + 2 * body[0]:
+    raise ValueError('truncated: SOS')
+  if body[0] != len(comps) or [body[1 + 2 * i] for i in range(body[0])] != [
+      c[0] for c in comps]:
+    raise NotImplementedError('a scan that does not hold all components in '
+                              'frame order')
+  if tuple(body[1 + 2 * body[0]:4 + 2 * body[0]]) != (0, 63, 0):
+    raise NotImplementedError('Ss, Se, Ah/Al other than 0, 63, 0')
+  selectors = [(body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15)
+               for i in range(body[0])]
+  for (td, ta), comp in zip(selectors, comps):
+    if td > 1 or ta > 1:
+      raise NotImplementedError('Huffman table ids above 1')
+    if (0, td) not in huffman or (1, ta) not in huffman:
+      raise ValueError('the scan refers to a Huffman table the file does '
+                       'not define')
+    if comp[3] not in qtables:
+      raise ValueError('component %d refers to quantisation table %d, which '
+                       'the file does not define' % (comp[0], comp[3]))
+  tables = []
+  for index in range(2):
+    if (0, index) not in huffman and (1, index) not in huffman:
+      tables.append(None)
+      continue
+    dc = huffman.get((0, index), (np.zeros(16, np.int64),
+                                  np.zeros(16, np.uint16)))
+    ac = huffman.get((1, index), (np.zeros(256, np.int64),
+                                  np.zeros(256, np.uint16)))
+    tables.append({'dc': dc[0], 'ac': ac[0], 'dc_codes': dc[1],
+                   'ac_codes': ac[1]})
+  return {'shape': (frame['h'], frame['w']), 'components': comps,
+          'sampling': sampling, 'qtables': qtables, 'tables': tables,
+          'selectors': selectors, 'segment_at': at}
+
+
+def frame_layout(shape, sampling):
+  """scan_layout for any frame this module reads: sampling is [(1, 1)] for a
+  gray file or [(H, V), (1, 1), (1, 1)] with H and V of the luma component 1
+  or 2 -- 4:4:4, 4:2:2 (2, 1), 4:4:0 (1, 2), 4:2:0 (2, 2).
+
+  The keys of scan_layout, equal to it array for array where it knows the
+  case ('subsampling' is (V, H) of the luma component, as utils.color takes
+  it), and for vtc_jfif_dc_accumulate 'order' int32 (rows,) -- the rows sorted
+  by component, then by scan order -- and 'start' uint8 (rows,), 1 where a
+  component's chain begins."""
+  try:
+    h, w = (int(v) for v in shape)
+    sampling = [(int(sh), int(sv)) for sh, sv in sampling]
+  except (TypeError, ValueError):
+    raise ValueError('shape must be (h, w) and sampling a list of (H, V)')
+  if not (1 <= h <= 65535 and 1 <= w <= 65535):
+    raise ValueError('a JFIF image is 1 .. 65535 pixels a side, got %r'
+                     % ((h, w),))
+  if sampling != [(1, 1)] and not (
+      len(sampling) == 3 and sampling[0][0] in (1, 2) and
+      sampling[0][1] in (1, 2) and sampling[1:] == [(1, 1), (1, 1)]):
+    raise NotImplementedError('sampling %r: one component, or luma 1 or 2 '
+                              'each way over 1 x 1 chroma' % (sampling,))
+  hmax = max(s[0] for s in sampling)
+  vmax = max(s[1] for s in sampling)
+  mcus_v, mcus_h = -(-h // (8 * vmax)), -(-w // (8 * hmax))
+  per_mcu = sum(sh * sv for sh, sv in sampling)
+  rows = mcus_v * mcus_h * per_mcu
+  my, mx = np.meshgrid(np.arange(mcus_v), np.arange(mcus_h), indexing='ij')
+  mcu_base = (my * mcus_h + mx) * per_mcu
+  component = np.zeros(rows, dtype=np.uint8)
+  pred = np.full(rows, -1, dtype=np.int32)
+  start = np.zeros(rows, dtype=np.uint8)
+  plane_shapes, grids, row_of_block, order = [], [], [], []
+  first = 0   # the component's first row inside an MCU
+  for c, (sh, sv) in enumerate(sampling):
+    plane_shapes.append((-(-h * sv // vmax), -(-w * sh // hmax)))
+    bh, bw = mcus_v * sv, mcus_h * sh
+    grids.append((bh, bw))
+    rob = np.zeros((bh, bw), dtype=np.int32)
+    for dy in range(sv):
+      for dx in range(sh):
+        rob[dy::sv, dx::sh] = mcu_base + first + dy * sh + dx
+    row_of_block.append(rob.reshape(-1))
+    mine = np.sort(rob.reshape(-1))   # the component's rows in scan order
+    component[mine] = c
+    pred[mine[1:]] = mine[:-1]
+    start[len(order) and sum(len(o) for o in order)] = 1
+    order.append(mine)
+    first += sh * sv
+  return {'shape': (h, w),
+          'subsampling': None if len(sampling) == 1 else (vmax, hmax),
+          'rows': rows, 'plane_shapes': plane_shapes, 'grids': grids,
+          'sampling': sampling, 'row_of_block': row_of_block,
+          'component': component,
+          'table_sel': (component > 0).astype(np.uint8), 'pred': pred,
+          'order': np.concatenate(order).astype(np.int32), 'start': start}
+
+
+def unstuff_bytes(data, capacity=None):
+  """(out, length, marker_at, dropped): `data` (a uint8 device tensor) up to
+  its first marker -- a 0xFF that no 0x00 follows -- with the 0x00 behind every
+  0xFF removed, as a uint8 device tensor of min(length, capacity) bytes;
+  marker_at is data.numel() when there is no marker; dropped counts the bytes
+  that did not fit under `capacity` (None: room for all).  One host read."""
+  lib = vtc_hip.load_library()
+  data = vtc_hip.require_device_tensor(data, 'data', torch.uint8)
+  if data.dim() != 1:
+    raise ValueError('data must be (n,), got shape %s' % (tuple(data.shape),))
+  data = data.contiguous()
+  capacity = data.numel() if capacity is None else int(capacity)
+  if capacity < 0:
+    raise ValueError('capacity must not be negative')
+  meta = torch.zeros(8, dtype=torch.int64, device=data.device)
+  out = _unstuff(lib, data, capacity, meta)
+  host = meta.cpu().numpy()
+  length, marker_at = int(host[0]), int(host[1])
+  return (out[:min(length, capacity)], length, marker_at,
+          int(host[2:3].view(np.int32)[0]))
+
+
+def _unstuff(lib, data, capacity, meta):
+  """Enqueues the unstuffing of `data` into a fresh tensor of `capacity`
+  bytes.  meta int64[8]: [0:2] out_len, [2] the dropped count (its low int32)."""
+  device = data.device
+  n = data.numel()
+  out = torch.empty(max(1, capacity), dtype=torch.uint8, device=device)
+  ws = vtc_hip.workspace(lib.vtc_jfif_unstuff_bytes_workspace_bytes(n), device)
+  vtc_hip.check(lib.vtc_jfif_unstuff_bytes(
+      vtc_hip.ptr(data) if n else None, n, vtc_hip.ptr(out), capacity,
+      vtc_hip.ptr(meta[0:2]), vtc_hip.ptr(meta[2:3]), vtc_hip.ptr(ws),
+      ws.numel(), vtc_hip.current_stream(device)), 'vtc_jfif_unstuff_bytes')
+  return out
+
+
+class _DecodeTables(_DeviceTables):
+  """_DeviceTables for a file that is read: where a pair carries the file's
+  own codewords ('dc_codes', 'ac_codes': parse_headers), those are used; a
+  DHT segment need not list the symbols of one length in ascending order."""
+
+  def __init__(self, tables, device):
+    _DeviceTables.__init__(self, tables, device)
+    ac_code = self.ac_code.cpu().numpy().view(np.uint16).copy()
+    dc_code = self.dc_code.cpu().numpy().view(np.uint16).copy()
+    for pair, table in enumerate(tables):
+      if table is not None and 'ac_codes' in table:
+        ac_code[pair] = np.asarray(table['ac_codes'], dtype=np.uint16)
+        dc_code[pair] = np.asarray(table['dc_codes'], dtype=np.uint16)
+    self.ac_code = _upload(ac_code.view(np.int16), device)
+    self.dc_code = _upload(dc_code.view(np.int16), device)
+
+
+def _slots(layout, selectors):
+  """(slot_dc, slot_ac) uint8: the table of each block position of an MCU."""
+  sampling = layout['sampling']
+  if len(selectors) != len(sampling):
+    raise ValueError('selectors must hold one (Td, Ta) per component (%d)'
+                     % len(sampling))
+  slot_dc, slot_ac = [], []
+  for (sh, sv), (td, ta) in zip(sampling, selectors):
+    if td not in (0, 1) or ta not in (0, 1):
+      raise ValueError('table selectors are 0 or 1, got %r' % ((td, ta),))
+    slot_dc += [td] * (sh * sv)
+    slot_ac += [ta] * (sh * sv)
+  return (np.array(slot_dc, dtype=np.uint8), np.array(slot_ac, dtype=np.uint8))
+
+
+def _unpack(lib, segment, layout, tables, selectors, status):
+  """Enqueues the unpacking of `segment` into a fresh (rows, 64) tensor.
+  status: int64[4] on the device."""
+  device = segment.device
+  rows = layout['rows']
+  slot_dc, slot_ac = _slots(layout, selectors)
+  dev = tables if isinstance(tables, _DeviceTables) else _DecodeTables(
+      tables, device)
+  levels = torch.empty((rows, 64), dtype=torch.int32, device=device)
+  ws = vtc_hip.workspace(
+      lib.vtc_jfif_unpack_workspace_bytes(segment.numel()), device)
+  nslots = len(slot_dc)
+  slot_dc, slot_ac = _upload(slot_dc, device), _upload(slot_ac, device)
+  vtc_hip.check(lib.vtc_jfif_unpack(
+      vtc_hip.ptr(segment), segment.numel(), vtc_hip.ptr(slot_dc),
+      vtc_hip.ptr(slot_ac), nslots,
+      vtc_hip.ptr(dev.ac_code), vtc_hip.ptr(dev.ac_len),
+      vtc_hip.ptr(dev.dc_code), vtc_hip.ptr(dev.dc_len), vtc_hip.ptr(levels),
+      rows, vtc_hip.ptr(status), vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), 'vtc_jfif_unpack')
+  return levels
+
+
+def unpack_scan(segment, layout, tables, selectors=None):
+  """(levels, status): the (rows, 64) int32 device levels of an unstuffed
+  entropy-coded `segment` (a uint8 device tensor), DIFF in column 0, by
+  self-synchronising parallel Huffman decoding; status the four integers of
+  vtc_jfif_unpack -- 1 + bit of the first malformed token or 0, blocks
+  completed, bit after block `rows` or -1, synchronisation rounds.  tables as
+  tables_from_counts or parse_headers give them; selectors [(Td, Ta)] per
+  component, by default (0, 0) for the first and (1, 1) for the others.  One
+  host read; nothing is raised for a malformed stream."""
+  lib = vtc_hip.load_library()
+  segment = vtc_hip.require_device_tensor(segment, 'segment', torch.uint8)
+  if segment.dim() != 1 or segment.numel() < 1:
+    raise ValueError('segment must be (n,) with n >= 1, got shape %s'
+                     % (tuple(segment.shape),))
+  if selectors is None:
+    selectors = [(min(c, 1), min(c, 1))
+                 for c in range(len(layout['sampling']))]
+  status = torch.zeros(4, dtype=torch.int64, device=segment.device)
+  levels = _unpack(lib, segment.contiguous(), layout, tables, selectors,
+                   status)
+  return levels, status.cpu().tolist()
+
+
+def _dc_accumulate(lib, levels, layout):
+  device = levels.device
+  d = levels.shape[0]
+  order = np.ascontiguousarray(layout['order'], dtype=np.int32).reshape(-1)
+  start = np.ascontiguousarray(layout['start'], dtype=np.uint8).reshape(-1)
+  if order.shape[0] != d or start.shape[0] != d:
+    raise ValueError('order and start must have one entry per row (%d)' % d)
+  ws = vtc_hip.workspace(lib.vtc_jfif_dc_accumulate_workspace_bytes(d), device)
+  order, start = _upload(order, device), _upload(start, device)
+  vtc_hip.check(lib.vtc_jfif_dc_accumulate(
+      vtc_hip.ptr(levels), d, vtc_hip.ptr(order), vtc_hip.ptr(start),
+      vtc_hip.ptr(ws), ws.numel(),
+      vtc_hip.current_stream(device)), 'vtc_jfif_dc_accumulate')
+  return levels
+
+
+def dc_accumulate(levels, layout):
+  """Undoes DC prediction in place: column 0 of the (rows, 64) int32 device
+  `levels` goes from DIFF to the DC level, along layout['order'] with a new
+  chain where layout['start'] is set (frame_layout), as a segmented scan on
+  the device.  Returns levels.  Only enqueues."""
+  lib = vtc_hip.load_library()
+  if _levels(levels) is not levels:
+    raise ValueError('levels must be contiguous: it is updated in place')
+  return _dc_accumulate(lib, levels, layout)
+
+
+def decode_bytes(data):
+  """(image, info) of the bytes of one baseline JFIF file: the (h, w) float32
+  device plane of a gray file, or the (h, w, 3) RGB image of a colour one --
+  planes through inverse_dct, chroma back to full resolution with the triangle
+  filter of utils.color.merge_planes by the luma component's (V, H), RGB
+  clamped to [0, 255].
+
+  The headers are walked on the host (parse_headers), which also finds where
+  the segment ends; unstuffing, the parallel Huffman decode, the DC scan and
+  the inverse DCT run on the device, with one host read of the status records.
+  info holds 'levels' (the (rows, 64) int32 device tensor in scan order,
+  absolute DC), 'layout' (frame_layout), 'qtables' (one uint16[64] per
+  component), 'planes', 'rounds' (synchronisation rounds of the decode),
+  'trailing_bits_are_ones' (the pad bits of the last byte, T.81 F.1.2.3) and
+  'headers'.  ValueError for a malformed or truncated segment, for bytes left
+  over, and for anything but EOI behind the segment."""
+  from utils import color
+  lib = vtc_hip.load_library()
+  data = bytes(data)
+  headers = parse_headers(data)
+  layout = frame_layout(headers['shape'], headers['sampling'])
+  at = headers['segment_at']
+  found = _MARKER_IN_SEGMENT.search(data, at)
+  if found is None:
+    raise ValueError('truncated: no marker behind the entropy-coded segment')
+  marker_at = found.start() - at
+  follows = data[found.start() + 1]
+  if 0xD0 <= follows <= 0xD7:
+    raise ValueError('a restart marker (RST%d) inside the scan: restart '
+                     'intervals are not read' % (follows - 0xD0))
+  if follows != 0xD9:
+    raise ValueError('marker 0x%02x behind the entropy-coded segment where '
+                     'EOI should be' % follows)
+  seg_bytes = marker_at - data.count(b'\xff\x00', at, at + marker_at)
+  if seg_bytes < 1:
+    raise ValueError('truncated: an empty entropy-coded segment')
+  device = torch.device('cuda', torch.cuda.current_device())
+  # the marker travels too: the device finds it again (a writable copy)
+  stuffed = _upload(np.array(np.frombuffer(
+      data, dtype=np.uint8, count=marker_at + 2, offset=at)), device)
+  meta = torch.zeros(8, dtype=torch.int64, device=device)
+  segment = _unstuff(lib, stuffed, seg_bytes, meta)[:seg_bytes]
+  levels = _unpack(lib, segment, layout, headers['tables'],
+                   headers['selectors'], meta[4:8])
+  _dc_accumulate(lib, levels, layout)
+  qtables = [headers['qtables'][c[3]] for c in headers['components']]
+  planes = [inverse_dct(levels, layout['plane_shapes'][c], layout['grids'][c],
+                        qtables[c], layout['row_of_block'][c])
+            for c in range(len(qtables))]
+  host = meta.cpu().numpy()
+  dropped = int(host[2:3].view(np.int32)[0])
+  if (int(host[0]), int(host[1]), dropped) != (seg_bytes, marker_at, 0):
+    raise ValueError('the device unstuffed %d bytes up to offset %d (%d '
+                     'dropped), the host counted %d up to %d'
+                     % (host[0], host[1], dropped, seg_bytes, marker_at))
+  malformed, blocks, end, rounds = (int(v) for v in host[4:8])
+  if malformed:
+    raise ValueError('malformed token at bit %d of the entropy-coded segment '
+                     '(block %d of %d)' % (malformed - 1, blocks,
+                                           layout['rows']))
+  if blocks < layout['rows'] or end < 0:
+    raise ValueError('truncated: the segment holds %d of %d blocks'
+                     % (blocks, layout['rows']))
+  left = 8 * seg_bytes - end
+  if left < 0:
+    raise ValueError('truncated: the last token needs %d bits beyond the '
+                     'segment' % -left)
+  if left >= 8:
+    raise ValueError('%d bits are left over behind block %d'
+                     % (left, layout['rows']))
+  last = 0xFF if data[at + marker_at - 2:at + marker_at] == b'\xff\x00' else (
+      data[at + marker_at - 1])
+  info = {'levels': levels, 'layout': layout, 'qtables': qtables,
+          'planes': planes, 'rounds': rounds,
+          'trailing_bits_are_ones': last & ((1 << left) - 1) == (1 << left) - 1,
+          'headers': headers}
+  if len(planes) == 1:
+    return planes[0], info
+  return color.merge_planes(planes, layout['shape'], layout['subsampling'],
+                            upsampling='triangle', clamp=(0.0, 255.0)), info
+
+
+def read_jpeg(path):
+  """(image, info) of the baseline JFIF file at `path`: decode_bytes of its
+  bytes."""
+  with open(path, 'rb') as f:
+    return decode_bytes(f.read())
+
+
 def rate_distortion_image(image, quality=75, subsampling=(2, 2),
-                          qtables=None):
+                          qtables=None, from_stream=False):
   """The JPEG point of a rate-distortion curve: `image` ((h, w) gray or
   (h, w, 3) RGB, samples in [0, 255]) is written as a JFIF file and decoded
-  from its levels.
+  from its levels -- or, with from_stream, from the bytes of the file through
+  decode_bytes, the way any reader of the file sees it; info['decoded_from']
+  is then 'bytes'.
 
   Returns, in the order of utils.jpeg.rate_distortion_image,
   {'bits_per_pixel', 'pSNR', 'SSIM', 'tables'} and then 'bytes' and 'info':
@@ -680,7 +1163,11 @@ def rate_distortion_image(image, quality=75, subsampling=(2, 2),
     data, info = encode_gray(image, quality, qtables)
   else:
     data, info = encode_rgb(image, subsampling, quality, qtables)
-  decoded = decode_levels(info)
+  if from_stream:
+    decoded = decode_bytes(data)[0]
+    info['decoded_from'] = 'bytes'
+  else:
+    decoded = decode_levels(info)
   original = image.contiguous()
   if original.dim() == 2:
     pair = original[None], decoded[None]

@@ -3,7 +3,7 @@ Host-side binding of libvtc_hip.so (the C ABI declared in include/vtc_hip.h
 include/vtc_image.h, include/vtc_codec.h, include/vtc_decode.h,
 include/vtc_quality.h, include/vtc_stats.h, include/vtc_quant.h,
 include/vtc_vq.h, include/vtc_index_code.h, include/vtc_index_decode.h and
-include/vtc_index_ans.h; include/vtc_vq_large.h and the two headers under
+include/vtc_index_ans.h; include/vtc_vq_large.h and the headers under
 include/ext/ are named at their tables).
 
 PyTorch is used here for what it is good at on ROCm -- device memory, the
@@ -425,6 +425,29 @@ JFIF_BINDINGS = {
                                     _vp]),
 }
 
+JFIF_DECODE_ABI_VERSION = 1   # VTC_JFIF_DECODE_ABI_VERSION
+JFIF_SUBSEQ_BYTES = 128       # VTC_JFIF_SUBSEQ_BYTES
+JFIF_SUBSEQ_PER_GROUP = 256   # VTC_JFIF_SUBSEQ_PER_GROUP
+JFIF_DC_TILE = 256            # VTC_JFIF_DC_TILE
+JFIF_MAX_SLOTS = 10           # VTC_JFIF_MAX_SLOTS
+
+# The sixteenth header, include/ext/vtc_jfif_decode.h (same library): the
+# device half of a baseline JFIF reader -- byte unstuffing, the entropy-coded
+# segment back to levels by self-synchronising parallel Huffman decoding, DC
+# prediction undone.  Under include/ext/ and named ..._BINDINGS for the reason
+# given above.
+JFIF_DECODE_BINDINGS = {
+    'vtc_jfif_decode_abi_version': (_i32, []),
+    'vtc_jfif_unstuff_bytes_workspace_bytes': (_sz, [_i64]),
+    'vtc_jfif_unstuff_bytes': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                      _sz, _vp]),
+    'vtc_jfif_unpack_workspace_bytes': (_sz, [_i64]),
+    'vtc_jfif_unpack': (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                               _vp, _i64, _vp, _vp, _sz, _vp]),
+    'vtc_jfif_dc_accumulate_workspace_bytes': (_sz, [_i64]),
+    'vtc_jfif_dc_accumulate': (_i32, [_vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+}
+
 
 class VtcHipError(RuntimeError):
   pass
@@ -446,7 +469,7 @@ def load_library():
                 QUANT_SIGNATURES, VQ_SIGNATURES, INDEX_CODE_SIGNATURES,
                 INDEX_DECODE_SIGNATURES, INDEX_ANS_SIGNATURES,
                 VQ_LARGE_SIGNATURES, INDEX_ANS_SPLIT_BINDINGS,
-                COLOR_BINDINGS, JFIF_BINDINGS):
+                COLOR_BINDINGS, JFIF_BINDINGS, JFIF_DECODE_BINDINGS):
     for name, (restype, argtypes) in table.items():
       fn = getattr(lib, name)   # AttributeError if the export is missing
       fn.restype = restype
@@ -482,6 +505,8 @@ def load_library():
     raise ImportError('libvtc_hip.so colour ABI version mismatch')
   if lib.vtc_jfif_abi_version() != JFIF_ABI_VERSION:
     raise ImportError('libvtc_hip.so JFIF ABI version mismatch')
+  if lib.vtc_jfif_decode_abi_version() != JFIF_DECODE_ABI_VERSION:
+    raise ImportError('libvtc_hip.so JFIF decode ABI version mismatch')
   _lib = lib
   return lib
 
