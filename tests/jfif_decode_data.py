@@ -102,36 +102,82 @@ def _extend(value, size):
   return value if value >> (size - 1) else value - (1 << size) + 1
 
 
-def sequential_unpack(segment, slot_dc, slot_ac, arrays, rows):
+def _codewords(arrays, kind, t):
+  """[(left-aligned 16-bit key, length, symbol)] of one table: a length above
+  16 reads as 16, bits of the code above the length fall off."""
+  out = []
+  for s in range(arrays[kind + '_len'].shape[1]):
+    length = min(int(arrays[kind + '_len'][t, s]), 16)
+    if length:
+      code = int(arrays[kind + '_code'][t, s]) & (1 << length) - 1
+      out.append((code << (16 - length), length, s))
+  return out
+
+
+def shortest_codeword_rule(arrays):
+  """rule(kind, t, w) -> (symbol, length) of the shortest codeword of table
+  (kind, t) that the 16-bit window w starts with, (None, 0) when none does.
+  In a prefix-free table it is the only one."""
+  books = {(kind, t): {(length, key >> (16 - length)): s
+                       for key, length, s in _codewords(arrays, kind, t)}
+           for kind in ('dc', 'ac') for t in range(2)}
+
+  def rule(kind, t, w):
+    for length in range(1, 17):
+      hit = books[(kind, t)].get((length, w >> (16 - length)))
+      if hit is not None:
+        return hit, length
+    return None, 0
+  return rule
+
+
+def decode_table_rule(arrays, lookup_bits=9):
+  """The rule of the device's decode tables, which also says what a table
+  that is not prefix-free decodes to.  The codewords are sorted by (key,
+  length, symbol).  Every codeword of at most lookup_bits bits claims the
+  lookup entries of the prefixes that start with it, the later one in sorted
+  order winning; a window whose entry is claimed takes that codeword.  Any
+  other window takes the last sorted codeword whose key is <= the window, if
+  the window starts with it, and nothing otherwise."""
+  tables = {}
+  for kind in ('dc', 'ac'):
+    for t in range(2):
+      entries = sorted(_codewords(arrays, kind, t))
+      lookup = {}
+      for key, length, s in entries:
+        if length <= lookup_bits:
+          first = key >> (16 - lookup_bits)
+          for q in range(1 << (lookup_bits - length)):
+            lookup[first + q] = (s, length)
+      tables[(kind, t)] = (entries, lookup)
+
+  def rule(kind, t, w):
+    entries, lookup = tables[(kind, t)]
+    hit = lookup.get(w >> (16 - lookup_bits))
+    if hit is not None:
+      return hit
+    below = [e for e in entries if e[0] <= w]
+    if not below or (below[-1][0] ^ w) >> (16 - below[-1][1]):
+      return None, 0
+    return below[-1][2], below[-1][1]
+  return rule
+
+
+def sequential_unpack(segment, slot_dc, slot_ac, arrays, rows, rule=None):
   """(levels int32 (rows, 64) with DIFF in column 0, [status0, status1,
   status2]) of the decoder include/ext/vtc_jfif_decode.h states: bits beyond
   the segment read as ones, a token must start inside the segment, the first
-  malformed token stops the walk."""
+  malformed token stops the walk.  rule(kind, t, w): the codeword a 16-bit
+  window starts with, shortest_codeword_rule(arrays) by default."""
   segment = bytes(segment)
   total = 8 * len(segment)
   padded = segment + b'\xff' * 8
+  if rule is None:
+    rule = shortest_codeword_rule(arrays)
 
   def peek(p, n):    # n <= 16 bits from bit p on
     word = int.from_bytes(padded[p >> 3:(p >> 3) + 4], 'big')
     return word >> (32 - (p & 7) - n) & (1 << n) - 1
-
-  books = {}
-  for kind, size in (('dc', 16), ('ac', 256)):
-    for t in range(2):
-      book = {}
-      for s in range(size):
-        length = min(int(arrays[kind + '_len'][t, s]), 16)
-        if length:
-          book[(length, int(arrays[kind + '_code'][t, s]) &
-                (1 << length) - 1)] = s
-      books[(kind, t)] = book
-
-  def symbol(book, p):
-    for length in range(1, 17):
-      hit = book.get((length, peek(p, length)))
-      if hit is not None:
-        return hit, length
-    return None, 0
 
   levels = np.zeros((rows, 64), dtype=np.int32)
   p, row = 0, 0
@@ -142,7 +188,7 @@ def sequential_unpack(segment, slot_dc, slot_ac, arrays, rows):
       if p >= total:
         return levels, [0, row, -1]
       if z == 0:
-        s, length = symbol(books[('dc', 1 if slot_dc[slot] else 0)], p)
+        s, length = rule('dc', 1 if slot_dc[slot] else 0, peek(p, 16))
         if s is None or s > 11:
           return levels, [p + 1, row, -1]
         if s:
@@ -150,7 +196,7 @@ def sequential_unpack(segment, slot_dc, slot_ac, arrays, rows):
         p += length + s
         z = 1
         continue
-      s, length = symbol(books[('ac', 1 if slot_ac[slot] else 0)], p)
+      s, length = rule('ac', 1 if slot_ac[slot] else 0, peek(p, 16))
       if s is None:
         return levels, [p + 1, row, -1]
       run, size = s >> 4, s & 15
@@ -270,6 +316,65 @@ def geometric_tail_tables():
   table = {'dc': truth.package_merge(dc), 'ac': truth.package_merge(ac)}
   assert table['ac'].max() == 16 and table['ac'].min() >= 1
   return [table, None]
+
+
+# AC table of overlapping_tables(), symbol -> length.  Canonical codewords
+# go by (length, symbol): 0x13 gets 111111100, the 11-bit ones follow from
+# 11111110100 on, so the fifth of them, 0x22, is 11111111000.
+_OVERLAP_AC = {0x00: 2, 0x01: 2, 0x02: 3, 0x03: 3, 0x11: 4, 0x07: 4, 0x08: 4,
+               0x04: 5, 0x12: 6, 0x21: 7, 0x13: 9, 0x05: 11, 0x06: 11,
+               0x15: 11, 0x16: 11, 0x22: 11, 0x41: 12}
+OVERLAP_PREFIX, OVERLAP_LONGER = 0x14, 0x13
+OVERLAP_TWIN, OVERLAP_FIRST = 0x32, 0x22
+
+
+def overlapping_tables():
+  """table_arrays of one pair that is not prefix-free: a canonical DC table;
+  a canonical AC table plus symbol OVERLAP_PREFIX, whose codeword 11111110 is
+  the head of the 9-bit codeword of OVERLAP_LONGER (both inside a 9-bit
+  lookup) and of four 11-bit codewords, and plus symbol OVERLAP_TWIN under the
+  11-bit codeword of OVERLAP_FIRST, which no shorter codeword is a head of."""
+  ac = np.zeros(256, dtype=np.int64)
+  for symbol, length in _OVERLAP_AC.items():
+    ac[symbol] = length
+  dc = np.array([2, 2, 2, 3, 3] + [0] * 11, dtype=np.int64)
+  arrays = table_arrays([{'dc': dc, 'ac': ac}, None])
+  assert arrays['ac_code'][0, OVERLAP_LONGER] == 0b111111100
+  assert arrays['ac_code'][0, OVERLAP_FIRST] == 0b11111111000
+  arrays['ac_len'][0, OVERLAP_PREFIX] = 8
+  arrays['ac_code'][0, OVERLAP_PREFIX] = 0b11111110
+  arrays['ac_len'][0, OVERLAP_TWIN] = 11
+  arrays['ac_code'][0, OVERLAP_TWIN] = 0b11111111000
+  return arrays
+
+
+def overlapping_segment(arrays, rows, seed, tokens=11):
+  """Bytes of `rows` blocks written from overlapping_tables(): a DC token,
+  `tokens` AC tokens drawn from all its symbols with random value bits, an
+  end of block; ones to the byte boundary.  What a decoder reads back is the
+  decode rule's business: it loses its place behind the first ambiguous
+  codeword and finds it again, as Huffman decoders do."""
+  rs = np.random.RandomState(seed)
+  # the codewords the added ones touch are written often
+  symbols = sorted(set(_OVERLAP_AC) - {0x00}) + 3 * [
+      OVERLAP_PREFIX, OVERLAP_LONGER, OVERLAP_TWIN, OVERLAP_FIRST, 0x05]
+  bits = []
+
+  def put(value, n):
+    bits.extend(value >> (n - 1 - i) & 1 for i in range(n))
+
+  def token(kind, symbol):
+    put(int(arrays[kind + '_code'][0, symbol]),
+        int(arrays[kind + '_len'][0, symbol]))
+    put(int(rs.randint(0, 1 << 15)) & (1 << (symbol & 15)) - 1, symbol & 15)
+
+  for _ in range(rows):
+    token('dc', int(rs.randint(0, 5)))
+    for _ in range(tokens):
+      token('ac', symbols[rs.randint(0, len(symbols))])
+    token('ac', 0x00)
+  bits += [1] * (-len(bits) % 8)
+  return np.packbits(np.array(bits, dtype=np.uint8)).tobytes()
 
 
 # ------------------------------------------------------------ header bytes

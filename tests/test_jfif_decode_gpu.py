@@ -477,6 +477,46 @@ def test_bytes_that_are_no_stream_at_all(device):
     assert np.array_equal(got.cpu().numpy()[:done], want[:done])
 
 
+def test_tables_that_are_not_prefix_free(device):
+  """vtc_jfif_unpack reports no bad table: it decodes by the rule of its decode
+  tables (dd.decode_table_rule), the same bits at every call.  One workgroup,
+  three subsequences.  The expectation was fixed on the commit before the
+  decode table was stated once (csrc/prefix_table.h), which gave status
+  [0, 16, 864, 1] and these levels: profiles/prefix_table_refactor.txt."""
+  jfif = _jfif()
+  rows = 16
+  arrays = dd.overlapping_tables()
+  raw = dd.overlapping_segment(arrays, rows, seed=26)
+  assert 2 * SUBSEQ < len(raw) <= 3 * SUBSEQ
+  rule, seen = dd.decode_table_rule(arrays), set()
+
+  def recording(kind, t, w):
+    hit = rule(kind, t, w)
+    seen.add((kind, hit[0]))
+    return hit
+  want, want_status = dd.sequential_unpack(raw, [0], [0], arrays, rows,
+                                           recording)
+  # the walk completes, and meets: the prefix where only longer codewords
+  # share its lookup entries, the longer one where both claim them, the twin
+  # (the later of two equal keys), a plain predecessor search
+  assert want_status[0] == 0 and want_status[1] == rows
+  assert {('ac', dd.OVERLAP_PREFIX), ('ac', dd.OVERLAP_LONGER),
+          ('ac', dd.OVERLAP_TWIN), ('ac', 0x41)} <= seen
+  assert ('ac', dd.OVERLAP_FIRST) not in seen and ('ac', 0x05) not in seen
+  # a decoder that takes the shortest match reads other levels
+  assert not np.array_equal(
+      want, dd.sequential_unpack(raw, [0], [0], arrays, rows)[0])
+  dev = jfif._DecodeTables([None, None], device)
+  for name in ('ac_code', 'dc_code'):
+    setattr(dev, name, _dev(arrays[name].view(np.int16), device))
+  for name in ('ac_len', 'dc_len'):
+    setattr(dev, name, _dev(arrays[name], device))
+  got, status = _unpack(device, raw, rows, dev)   # two calls, equal bits
+  print('status', status, 'want', want_status)
+  assert status[:3] == want_status
+  assert np.array_equal(got.cpu().numpy(), want)
+
+
 # -------------------------------------------------------------- R-D point
 def test_rate_distortion_image_from_stream(device):
   jfif = _jfif()

@@ -118,15 +118,6 @@ __device__ __forceinline__ unsigned lower_lanes(u64 mask, int lane) {
   return (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
-__device__ __forceinline__ u64 wave_min_u64(u64 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const u64 o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
 // ---- encoding -------------------------------------------------------------------
 // pack: the stream's slot, and the words the caller's size leaves room for.
 // sizes: no slot, and the cursor counts down from 0.
@@ -204,7 +195,7 @@ __device__ __forceinline__ void finish_encode(
   }
   const int count = wave_sum_int(uncodable);
   if (count) {   // the whole wave
-    first = wave_min_u64(first);
+    first = wave_min(first);
     if (lane == 0) {
       atomicAdd(&status[0], (u64)count);
       atomicMin(&status[1], first);

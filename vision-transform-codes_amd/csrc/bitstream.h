@@ -1,6 +1,7 @@
-// The bit writer shared by the packers of jpeg_codec.hip and index_code.hip,
-// and the bit reader shared by the decoders of jpeg_decode.hip and
-// index_decode.hip.
+// The bit writer shared by the packers of jpeg_codec.hip, index_code.hip and
+// jfif.hip, and the bit reader of one lane shared by the decoders of
+// jpeg_decode.hip and index_decode.hip (through prefix_table.h, which
+// jfif_decode.hip includes as well: six users).
 #pragma once
 
 #include <hip/hip_runtime.h>

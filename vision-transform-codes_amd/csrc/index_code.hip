@@ -83,15 +83,6 @@ __device__ __forceinline__ long long wave_sum_ll(long long v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
-__device__ __forceinline__ unsigned long long wave_min_ull(
-    unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // Uncodable entries seen by one lane.
 struct Uncodable {
@@ -126,7 +117,7 @@ __device__ __forceinline__ int step_entry(const int32_t* __restrict__ indices,
 __device__ __forceinline__ void report(const Uncodable& bad, long long dropped,
                                        int lane, unsigned long long* status) {
   const long long count = wave_sum_ll(bad.count);
-  const unsigned long long first = wave_min_ull(bad.first);
+  const unsigned long long first = wave_min(bad.first);
   dropped = wave_sum_ll(dropped);
   if (lane != 0) return;
   if (count) {

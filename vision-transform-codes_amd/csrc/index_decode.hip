@@ -10,27 +10,25 @@
 //
 // Four launches per call, all on the caller's stream:
 //   1. index_unpack_begin_kernel: status and the workspace's prefix flag
-//   2. index_tables_kernel, one block per column: left-aligns the column's
-//      codewords to 64 bits, sorts them in LDS (bitonic over the next power of
-//      two, absent entries last, 1024 threads: the launch's time is the
-//      latency of this one sort), checks neighbours for prefix or equality and
-//      builds a first-level lookup of kLutBits bits, into the workspace
+//   2. index_tables_kernel, one block per column: the column's decode table
+//      of prefix_table.h, into the workspace (sorted over the next power of
+//      two by 1024 threads: the launch's time is the latency of this one sort)
 //   3. index_unpack_kernel: every lane walks its row; a wave collects 64 rows
 //      x kTile columns in LDS and stores them with consecutive lanes on
 //      consecutive addresses
-//   4. index_unpack_end_kernel: the minimum of status[1] and the flag into status[2]
+//   4. index_unpack_end_kernel: the minimum of status[1] and the flag into
+//      status[2]
 //
 // A codeword of at most kLutBits bits is one read of the column's lookup; a
-// longer one is found by predecessor search in the sorted array: for a
-// prefix-free code the match is the largest left-aligned codeword <= the
-// window, provided the window really starts with it.  The tables (up to
-// 4096 * 4096 * 12 bytes plus lookups) stay in global memory, where they are
-// cache resident: every row reads them.
+// longer one is found by predecessor search in the sorted array.  The tables
+// (up to 4096 * 4096 * 12 bytes plus lookups) stay in global memory, where
+// they are cache resident: every row reads them.
 #include <limits.h>
 
 #include "../../include/vtc_index_decode.h"
 #include "bitstream.h"
 #include "common.h"
+#include "prefix_table.h"
 
 namespace vtc {
 namespace {
@@ -40,24 +38,36 @@ constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kTableBlock = 1024;   // threads that sort one column's table
 constexpr int kMaxColumns = VTC_INDEX_CODE_MAX_COLUMNS;
 constexpr int kMaxSymbols = VTC_INDEX_CODE_MAX_SYMBOLS;
-constexpr int kLutBits = VTC_INDEX_DECODE_LOOKUP_BITS;
-constexpr int kLutSize = 1 << kLutBits;
 constexpr int kMaxCodeBits = 64;
 constexpr int kTile = 32;               // columns a wave collects before it stores
 constexpr int kTileStride = kTile + 1;  // odd: lane-per-row writes hit 64 banks
 
 // meta word of a codeword: an explicit valid bit (the empty codeword of symbol
 // 0 would otherwise be 0, "no codeword"), length 0 .. 64, symbol 0 .. 4095.
-constexpr unsigned kValid = 1u << 31;
-__host__ __device__ constexpr unsigned meta_of(int len, int symbol) {
-  return kValid | (unsigned)len << 12 | (unsigned)symbol;
-}
-__host__ __device__ constexpr int meta_len(unsigned meta) {
-  return (int)(meta >> 12 & 127u);
-}
-__host__ __device__ constexpr int meta_symbol(unsigned meta) {
-  return (int)(meta & 4095u);
-}
+struct IndexCode {
+  typedef u64 Key;
+  typedef uint32_t Meta;
+  static constexpr int kLutBits = VTC_INDEX_DECODE_LOOKUP_BITS;
+  static constexpr unsigned kValid = 1u << 31;
+  static __host__ __device__ constexpr unsigned make(int len, int symbol) {
+    return kValid | (unsigned)len << 12 | (unsigned)symbol;
+  }
+  static __host__ __device__ constexpr bool valid(unsigned m) {
+    return m & kValid;
+  }
+  static __host__ __device__ constexpr int len(unsigned m) {
+    return m >> 12 & 127u;
+  }
+  static __host__ __device__ constexpr int symbol(unsigned m) {
+    return m & 4095u;
+  }
+};
+typedef PrefixTable<IndexCode> Table;
+constexpr int kLutBits = Table::kLutBits;
+constexpr int kLutSize = Table::kLutSize;
+static_assert(Table::round_trips(0, 0) && Table::round_trips(64, 4095) &&
+                  Table::round_trips(0, 4095) && Table::round_trips(64, 0),
+              "valid | length << 12 | symbol");
 
 struct IndexDecodeLayout {
   u64* code;        // [m * kmax] left-aligned, sorted, column j from j * kmax
@@ -87,16 +97,7 @@ __global__ void index_unpack_end_kernel(IndexDecodeLayout ws, u64* status) {
   status[2] = bad == INT_MAX ? 0 : (u64)bad + 1;
 }
 
-// ---- table preparation ------------------------------------------------------
-// Codewords first, by (word, length, symbol): length sits above the symbol in
-// the meta word.  Absent entries (valid bit clear) last, equal among themselves.
-__device__ __forceinline__ bool sorts_before(u64 ka, unsigned ma, u64 kb,
-                                             unsigned mb) {
-  if ((ma ^ mb) & kValid) return (ma & kValid) != 0;
-  if (ka != kb) return ka < kb;
-  return ma < mb;
-}
-
+// ---- table preparation (prefix_table.h) -------------------------------------
 __global__ __launch_bounds__(kTableBlock) void index_tables_kernel(
     const u64* __restrict__ code, const uint8_t* __restrict__ len, int kmax,
     IndexDecodeLayout ws) {
@@ -119,9 +120,8 @@ __global__ __launch_bounds__(kTableBlock) void index_tables_kernel(
   for (int i = tid; i < n2; i += kTableBlock) {
     const int l = i < kmax ? len[base + i] : VTC_INDEX_CODE_ABSENT;
     if (l <= kMaxCodeBits) {
-      const u64 c = code[base + i];
-      key[i] = l ? c << (kMaxCodeBits - l) : 0;   // bits above `l` fall off
-      meta[i] = meta_of(l, i);
+      key[i] = Table::left_align(code[base + i], l);
+      meta[i] = IndexCode::make(l, i);
       ++mine;
     } else {
       key[i] = ~0ull;
@@ -131,55 +131,16 @@ __global__ __launch_bounds__(kTableBlock) void index_tables_kernel(
   if (mine) atomicAdd(&count, mine);
   __syncthreads();
 
-  // bitonic sort of n2 entries
-  for (int k = 2; k <= n2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < n2 / 2; t += kTableBlock) {
-        // the t-th index with bit j clear, and its partner
-        const int i = (t & ~(j - 1)) << 1 | (t & (j - 1));
-        const int p = i | j;
-        const u64 ka = key[i], kb = key[p];
-        const unsigned ma = meta[i], mb = meta[p];
-        const bool ascending = (i & k) == 0;
-        const bool swap = ascending ? sorts_before(kb, mb, ka, ma)
-                                    : sorts_before(ka, ma, kb, mb);
-        if (swap) {
-          key[i] = kb;
-          meta[i] = mb;
-          key[p] = ka;
-          meta[p] = ma;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  Table::sort<kTableBlock>(key, meta, n2);
   const int n = count;   // the codewords are entries 0 .. n - 1
 
-  // If a codeword is a prefix of any other, it is one of its successor in
-  // sorted order: neighbours suffice.  The empty codeword is a prefix of every
-  // other (and no shift by 64 is taken for it).
   for (int i = tid; i + 1 < n; i += kTableBlock) {
-    const u64 a = key[i], b = key[i + 1];
-    const int la = meta_len(meta[i]), lb = meta_len(meta[i + 1]);
-    if (la <= lb && (la == 0 || ((a ^ b) >> (kMaxCodeBits - la)) == 0)) {
-      atomicMin(&bad, base + meta_symbol(meta[i]));
-      if (la == lb) atomicMin(&bad, base + meta_symbol(meta[i + 1]));
-    }
+    const int offender = Table::prefix_violation(key, meta, i);
+    if (offender != INT_MAX) atomicMin(&bad, base + offender);
   }
   __syncthreads();
-
-  // first level: every kLutBits-bit prefix that starts with a short codeword.
-  // The code is prefix-free here, so the ranges of two codewords are disjoint.
-  if (bad == INT_MAX) {
-    for (int i = tid; i < n; i += kTableBlock) {
-      const int l = meta_len(meta[i]);
-      if (l > kLutBits) continue;
-      const int first = (int)(key[i] >> (kMaxCodeBits - kLutBits));
-      const int span = 1 << (kLutBits - l);
-      for (int q = 0; q < span; ++q)   // first + span <= kLutSize
-        lut[first + q] = meta[i];
-    }
-  }
+  if (bad == INT_MAX)   // prefix-free: the ranges are disjoint
+    Table::fill_lookup(lut, key, meta, n, tid, kTableBlock);
   __syncthreads();
 
   for (int i = tid; i < kmax; i += kTableBlock) {
@@ -195,29 +156,6 @@ __global__ __launch_bounds__(kTableBlock) void index_tables_kernel(
 }
 
 // ---- decoding -----------------------------------------------------------------
-// The codeword the window starts with, as a meta word; 0 when none does.
-// lut, code, meta: one column's arrays in global memory; n: its codewords.
-__device__ __forceinline__ unsigned match(const uint32_t* __restrict__ lut,
-                                          const u64* __restrict__ code,
-                                          const uint32_t* __restrict__ meta,
-                                          int n, u64 w) {
-  const unsigned e = lut[w >> (kMaxCodeBits - kLutBits)];   // kLutBits bits
-  if (e & kValid) return e;
-  int lo = 0, hi = n;   // lo: number of codewords <= w
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (code[mid] <= w)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  if (lo == 0) return 0;
-  const unsigned m = meta[lo - 1];
-  const int l = meta_len(m);
-  if (l && ((code[lo - 1] ^ w) >> (kMaxCodeBits - l))) return 0;
-  return m;
-}
-
 __global__ __launch_bounds__(kBlock) void index_unpack_kernel(
     const uint8_t* __restrict__ packed, int64_t packed_bytes,
     const long long* __restrict__ offsets, int64_t b, int m, int kmax,
@@ -256,17 +194,14 @@ __global__ __launch_bounds__(kBlock) void index_unpack_kernel(
       const int j = j0 + c;
       int32_t symbol = -1;
       if (ok) {
-        r.refill();
-        const unsigned e =
-            match(ws.lut + ((size_t)j << kLutBits), ws.code + (size_t)j * kmax,
-                  ws.meta + (size_t)j * kmax, ws.count[j], r.window64());
-        const int l = meta_len(e);
-        if (!(e & kValid) || l > r.avail64()) {
+        const unsigned e = Table::read(
+            r, ws.lut + ((size_t)j << kLutBits), ws.code + (size_t)j * kmax,
+            ws.meta + (size_t)j * kmax, ws.count[j]);
+        if (!IndexCode::valid(e)) {
           ok = false;   // no codeword, or one that passes the end
           malformed = true;
         } else {
-          r.consume(l);
-          symbol = meta_symbol(e);
+          symbol = IndexCode::symbol(e);
         }
       }
       tile[lane * kTileStride + c] = symbol;

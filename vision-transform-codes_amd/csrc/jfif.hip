@@ -20,6 +20,7 @@
 
 #include "../../include/ext/vtc_jfif.h"
 #include "bitstream.h"
+#include "block_scan.h"
 #include "common.h"
 
 namespace vtc {
@@ -48,15 +49,6 @@ __constant__ uint8_t kZigzagOf[64] = {
     20, 22, 33, 38, 46, 51, 55, 60,   //
     21, 34, 37, 47, 50, 56, 59, 61,   //
     35, 36, 48, 49, 57, 58, 62, 63};
-
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // ---- DCT ------------------------------------------------------------------
 // sum over k, ascending, of a[from + k * step] * basis[row * 8 + k] (or
@@ -307,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void block_bits_kernel(
   }
   over = wave_sum_int(over);
   if (lane == 0 && over) atomicAdd(&status[0], over);
-  missing = wave_min_int(missing);
+  missing = wave_min(missing);
   if (lane == 0 && missing != INT_MAX) atomicMin(&status[1], missing);
 }
 
@@ -386,35 +378,11 @@ __global__ __launch_bounds__(kBlock) void pack_kernel(
   }
   over = wave_sum_int(over + dropped);
   if (lane == 0 && over) atomicAdd(&status[0], over);
-  missing = wave_min_int(missing);
+  missing = wave_min(missing);
   if (lane == 0 && missing != INT_MAX) atomicMin(&status[1], missing);
 }
 
-// ---- byte stuffing: count, scan, scatter ------------------------------------
-// Exclusive prefix of `v` over the block's 256 threads; *total = block sum.
-// The shape of the offsets scan of jpeg_codec.hip.
-__device__ __forceinline__ long long block_exclusive_scan(long long v,
-                                                          long long* total) {
-  __shared__ long long wave_sums[kWavesPerBlock];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  long long incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wave_sums[wave] = incl;
-  __syncthreads();
-  long long before = 0, all = 0;
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    if (w < wave) before += wave_sums[w];
-    all += wave_sums[w];
-  }
-  __syncthreads();   // wave_sums is reused by the next call
-  *total = all;
-  return before + incl - v;
-}
-
+// ---- byte stuffing: count, scan, scatter (block_scan.h) ---------------------
 // The thread's kStuffItems bytes from `first` on (zeros beyond n) and how many
 // of them are 0xFF.
 __device__ __forceinline__ int load_stuff_items(const uint8_t* raw, int64_t n,
@@ -435,7 +403,7 @@ __global__ __launch_bounds__(kBlock) void stuff_tile_sums_kernel(
                         (int64_t)threadIdx.x * kStuffItems;
   uint8_t b[kStuffItems];
   long long total;
-  block_exclusive_scan(load_stuff_items(raw, n, first, b), &total);
+  block_exclusive_scan<kBlock>(load_stuff_items(raw, n, first, b), &total);
   if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -444,15 +412,7 @@ __global__ __launch_bounds__(kBlock) void stuff_tile_sums_kernel(
 __global__ __launch_bounds__(kBlock) void stuff_scan_kernel(
     long long* __restrict__ sums, int64_t tiles, int64_t n, int64_t capacity,
     long long* __restrict__ out_len, int32_t* __restrict__ status) {
-  long long carry = 0;
-  for (int64_t base = 0; base < tiles; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const long long v = i < tiles ? sums[i] : 0;
-    long long total;
-    const long long before = block_exclusive_scan(v, &total);
-    if (i < tiles) sums[i] = carry + before;
-    carry += total;
-  }
+  const long long carry = block_prefix_tile_sums<kBlock>(sums, tiles);
   if (threadIdx.x == 0) {
     const long long length = n + carry;
     const long long lost = length > capacity ? length - capacity : 0;
@@ -473,7 +433,7 @@ __global__ __launch_bounds__(kBlock) void stuff_write_kernel(
   const int marks = load_stuff_items(raw, n, first, b);
   long long total;
   long long at =
-      first + sums[blockIdx.x] + block_exclusive_scan(marks, &total);
+      first + sums[blockIdx.x] + block_exclusive_scan<kBlock>(marks, &total);
 #pragma unroll
   for (int k = 0; k < kStuffItems; ++k) {
     if (first + k >= n) break;

@@ -18,14 +18,14 @@
 // storing pass.  The workgroup's 32 KiB of the segment are staged in LDS as
 // big-endian words, one pad word per subsequence, so lanes that stand at the
 // same offset of their subsequences read 32 different banks; the four decode
-// tables (first level on kLutBits bits, predecessor search in the sorted
-// left-aligned codewords behind it, as jpeg_decode.hip does) are in LDS too.
+// tables (prefix_table.h, first level on 9 bits) are in LDS too.
 #include <limits.h>
 
 #include "../../include/ext/vtc_jfif.h"
 #include "../../include/ext/vtc_jfif_decode.h"
-#include "bitstream.h"
+#include "block_scan.h"
 #include "common.h"
+#include "prefix_table.h"
 
 namespace vtc {
 namespace {
@@ -33,49 +33,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / 64;
 
-// ---- block scans ------------------------------------------------------------
-// Exclusive prefix of `v` over the block's 256 threads; *total = block sum.
-// The shape of the stuffing scan of jfif.hip.
-__device__ __forceinline__ long long block_exclusive_scan(long long v,
-                                                          long long* total) {
-  __shared__ long long wave_sums[kWavesPerBlock];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  long long incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wave_sums[wave] = incl;
-  __syncthreads();
-  long long before = 0, all = 0;
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    if (w < wave) before += wave_sums[w];
-    all += wave_sums[w];
-  }
-  __syncthreads();   // wave_sums is reused by the next call
-  *total = all;
-  return before + incl - v;
-}
-
-__device__ __forceinline__ long long block_min(long long v) {
-  __shared__ long long wave_mins[kWavesPerBlock];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const long long o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  if (lane == 0) wave_mins[wave] = v;
-  __syncthreads();
-  long long all = wave_mins[0];
-  for (int w = 1; w < kWavesPerBlock; ++w)
-    all = wave_mins[w] < all ? wave_mins[w] : all;
-  __syncthreads();
-  return all;
-}
-
-// ---- byte unstuffing: count, scan, scatter ----------------------------------
+// ---- byte unstuffing: count, scan, scatter (block_scan.h) -------------------
 constexpr int kStuffItems = VTC_JFIF_STUFF_TILE / kBlock;
 static_assert(kStuffItems * kBlock == VTC_JFIF_STUFF_TILE, "tile = block * 8");
 
@@ -133,8 +91,8 @@ __global__ __launch_bounds__(kBlock) void unstuff_tile_kernel(
   load_unstuff_items(in, n, first, b);
   long long marker, total;
   const int zeros = scan_unstuff_items(b, n, first, n, &marker);
-  block_exclusive_scan(zeros, &total);
-  marker = block_min(marker);
+  block_exclusive_scan<kBlock>(zeros, &total);
+  marker = block_min<kBlock>(marker);
   if (threadIdx.x == 0) {
     ws.sums[blockIdx.x] = total;
     ws.marks[blockIdx.x] = marker;
@@ -147,16 +105,11 @@ __global__ __launch_bounds__(kBlock) void unstuff_scan_kernel(
     const uint8_t* __restrict__ in, int64_t n, UnstuffLayout ws, int64_t tiles,
     int64_t capacity, long long* __restrict__ out_len,
     int32_t* __restrict__ status) {
-  long long carry = 0, marker = n;
+  const long long carry = block_prefix_tile_sums<kBlock>(ws.sums, tiles);
+  long long marker = n;
   for (int64_t base = 0; base < tiles; base += kBlock) {
     const int64_t i = base + threadIdx.x;
-    const long long v = i < tiles ? ws.sums[i] : 0;
-    const long long m = i < tiles ? ws.marks[i] : n;
-    long long total;
-    const long long before = block_exclusive_scan(v, &total);
-    if (i < tiles) ws.sums[i] = carry + before;
-    carry += total;
-    const long long lowest = block_min(m);
+    const long long lowest = block_min<kBlock>(i < tiles ? ws.marks[i] : n);
     marker = lowest < marker ? lowest : marker;
   }
   __syncthreads();   // sums[] of this block are visible to all its threads
@@ -168,8 +121,8 @@ __global__ __launch_bounds__(kBlock) void unstuff_scan_kernel(
     uint8_t b[kStuffItems + 2];
     load_unstuff_items(in, n, first, b);
     long long unused, inside;
-    block_exclusive_scan(scan_unstuff_items(b, n, first, marker, &unused),
-                         &inside);
+    block_exclusive_scan<kBlock>(
+        scan_unstuff_items(b, n, first, marker, &unused), &inside);
     zeros = ws.sums[tile] + inside;
   }
   if (threadIdx.x == 0) {
@@ -195,8 +148,8 @@ __global__ __launch_bounds__(kBlock) void unstuff_write_kernel(
   load_unstuff_items(in, n, first, b);
   long long unused, total;
   const int zeros = scan_unstuff_items(b, n, first, marker, &unused);
-  long long at =
-      first - ws.sums[blockIdx.x] - block_exclusive_scan(zeros, &total);
+  long long at = first - ws.sums[blockIdx.x] -
+                 block_exclusive_scan<kBlock>(zeros, &total);
 #pragma unroll
   for (int k = 0; k < kStuffItems; ++k) {
     if (first + k >= marker) break;
@@ -346,8 +299,6 @@ constexpr int kStagedPadded = kStagedWords + kStagedWords / 32 + 1;
 constexpr int kTables = 4;   // DC 0, DC 1, AC 0, AC 1
 constexpr int kDcSymbols = 16, kAcSymbols = 256;
 constexpr int kCodes = 2 * kDcSymbols + 2 * kAcSymbols;
-constexpr int kLutBits = 9;
-constexpr int kLutSize = 1 << kLutBits;
 constexpr int kMaxCodeBits = 16;
 constexpr int kEob = 0x00, kZrl = 0xF0;
 constexpr int kAcCap = 10, kDcCap = 11;
@@ -355,9 +306,31 @@ constexpr int kAcCap = 10, kDcCap = 11;
 __host__ __device__ constexpr int table_base(int t) {
   return t < 2 ? t * kDcSymbols : 2 * kDcSymbols + (t - 2) * kAcSymbols;
 }
-__host__ __device__ constexpr int table_size(int t) {
-  return t < 2 ? kDcSymbols : kAcSymbols;
-}
+
+// meta word of a codeword: length << 8 | symbol (lengths 1 .. 16); 0 is no
+// codeword.
+struct JfifCode {
+  typedef uint16_t Key;
+  typedef uint16_t Meta;
+  static constexpr int kLutBits = 9;
+  static __host__ __device__ constexpr unsigned make(int len, int symbol) {
+    return (unsigned)len << 8 | (unsigned)symbol;
+  }
+  static __host__ __device__ constexpr bool valid(unsigned m) {
+    return m != 0;
+  }
+  static __host__ __device__ constexpr int len(unsigned m) {
+    return m >> 8;
+  }
+  static __host__ __device__ constexpr int symbol(unsigned m) {
+    return m & 255;
+  }
+};
+typedef PrefixTable<JfifCode> Table;
+constexpr int kLutSize = Table::kLutSize;
+static_assert(Table::round_trips(1, 0) && Table::round_trips(16, 255) &&
+                  Table::round_trips(1, 255) && Table::round_trips(16, 0),
+              "length << 8 | symbol");
 
 // The state at a boundary: bit position << 10 | coefficient index << 4 | block
 // position.  Inside a workgroup positions count from the group's first bit
@@ -396,69 +369,43 @@ struct UnpackLayout {
   }
 };
 
-// One block: sorts the codewords of each table, builds the first-level
-// lookups, and sets the cross-workgroup state to "nothing decoded yet".
+// One block: the four decode tables of prefix_table.h, and the
+// cross-workgroup state set to "nothing decoded yet".  A table that is not
+// prefix-free is not reported: it decodes by the same rule.
 __global__ __launch_bounds__(kBlock) void unpack_tables_kernel(
     const uint16_t* __restrict__ ac_code, const uint8_t* __restrict__ ac_len,
     const uint16_t* __restrict__ dc_code, const uint8_t* __restrict__ dc_len,
     UnpackLayout ws, int64_t groups) {
-  __shared__ uint16_t key[kCodes], sorted_key[kCodes], sorted_meta[kCodes];
-  __shared__ uint8_t len[kCodes];
+  __shared__ uint16_t key[kCodes], meta[kCodes];
   __shared__ uint16_t lut[kTables * kLutSize];
   __shared__ int count[kTables];
   const int tid = threadIdx.x;
   if (tid < kTables) count[tid] = 0;
-  for (int i = tid; i < kCodes; i += kBlock) {
-    const int t = i < table_base(2) ? i / kDcSymbols
-                                    : 2 + (i - table_base(2)) / kAcSymbols;
-    const int s = i - table_base(t);
-    int l = t < 2 ? dc_len[t * kDcSymbols + s] : ac_len[(t - 2) * kAcSymbols + s];
-    if (l > kMaxCodeBits) l = kMaxCodeBits;
-    const unsigned c =
-        t < 2 ? dc_code[t * kDcSymbols + s] : ac_code[(t - 2) * kAcSymbols + s];
-    len[i] = (uint8_t)l;
-    key[i] = l ? (uint16_t)(c << (kMaxCodeBits - l)) : 0;  // bits above l fall off
-    sorted_key[i] = 0;
-    sorted_meta[i] = 0;
-  }
   for (int i = tid; i < kTables * kLutSize; i += kBlock) lut[i] = 0;
   __syncthreads();
-  // rank sort by (key, length, symbol), each table on its own
   for (int i = tid; i < kCodes; i += kBlock) {
-    if (!len[i]) continue;
     const int t = i < table_base(2) ? i / kDcSymbols
                                     : 2 + (i - table_base(2)) / kAcSymbols;
-    const int base = table_base(t), n = table_size(t);
-    int rank = 0;
-    for (int j = base; j < base + n; ++j) {
-      if (!len[j]) continue;
-      const bool first = key[j] != key[i] ? key[j] < key[i]
-                         : len[j] != len[i] ? len[j] < len[i] : j < i;
-      rank += first;
-    }
-    sorted_key[base + rank] = key[i];   // ranks of a table are distinct
-    sorted_meta[base + rank] = (uint16_t)(len[i] << 8 | (i - base));
-    atomicAdd(&count[t], 1);
+    int l = t < 2 ? dc_len[i] : ac_len[i - table_base(2)];
+    if (l > kMaxCodeBits) l = kMaxCodeBits;
+    const unsigned c = t < 2 ? dc_code[i] : ac_code[i - table_base(2)];
+    key[i] = Table::left_align(c, l);
+    meta[i] = l ? JfifCode::make(l, i - table_base(t)) : 0;
+    if (l) atomicAdd(&count[t], 1);
   }
   __syncthreads();
-  // first level.  Prefix-free codewords fill disjoint ranges; where a table
-  // is not prefix-free the entries are filled in sorted order by ONE thread
-  // per table, so the lookup is still a function of the tables alone.
-  if (tid < kTables) {
-    const int base = table_base(tid);
-    for (int r = 0; r < count[tid]; ++r) {
-      const int l = sorted_meta[base + r] >> 8;
-      if (l > kLutBits) continue;
-      const int from = sorted_key[base + r] >> (kMaxCodeBits - kLutBits);
-      const int span = 1 << (kLutBits - l);   // from + span <= kLutSize
-      for (int q = 0; q < span; ++q)
-        lut[tid * kLutSize + from + q] = sorted_meta[base + r];
-    }
-  }
+  for (int t = 0; t < kTables; ++t)   // each table on its own
+    Table::sort<kBlock>(key + table_base(t), meta + table_base(t),
+                        t < 2 ? kDcSymbols : kAcSymbols);
+  // where ranges overlap the later codeword wins: one thread per table, so
+  // the lookup is a function of the tables alone
+  if (tid < kTables)
+    Table::fill_lookup(lut + tid * kLutSize, key + table_base(tid),
+                       meta + table_base(tid), count[tid], 0, 1);
   __syncthreads();
   for (int i = tid; i < kCodes; i += kBlock) {
-    ws.key[i] = sorted_key[i];
-    ws.meta[i] = sorted_meta[i];
+    ws.key[i] = key[i];
+    ws.meta[i] = meta[i];
   }
   for (int i = tid; i < kTables * kLutSize; i += kBlock) ws.lut[i] = lut[i];
   if (tid < kTables) ws.count[tid] = count[tid];
@@ -565,21 +512,8 @@ struct Window {
 // 0 when none does.
 __device__ __forceinline__ unsigned match(const GroupShared& sh, int t,
                                           unsigned w) {
-  const unsigned e = sh.lut[t * kLutSize + (w >> (kMaxCodeBits - kLutBits))];
-  if (e) return e;
-  const uint16_t* key = sh.key + table_base(t);
-  int lo = 0, hi = sh.count[t];   // lo: number of codewords <= w
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (key[mid] <= w)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  if (lo == 0) return 0;
-  const unsigned m = sh.meta[table_base(t) + lo - 1];
-  if ((key[lo - 1] ^ w) >> (kMaxCodeBits - (m >> 8))) return 0;
-  return m;
+  return Table::match(sh.lut + t * kLutSize, sh.key + table_base(t),
+                      sh.meta + table_base(t), sh.count[t], (uint16_t)w);
 }
 
 __device__ __forceinline__ int32_t extend(uint32_t window, int len, int size) {
@@ -626,7 +560,7 @@ __device__ __forceinline__ Token step(const GroupShared& sh, Window& win,
   const int table = dc ? (int)(slots.dc >> s.slot & 1u)
                        : 2 + (int)(slots.ac >> s.slot & 1u);
   const unsigned m = match(sh, table, w >> 16);
-  const int len = m ? (int)(m >> 8) : 1, symbol = (int)(m & 255);
+  const int len = m ? JfifCode::len(m) : 1, symbol = JfifCode::symbol(m);
   int advance = len;
   if (!m) {
     t.malformed = true;
@@ -737,7 +671,8 @@ __global__ __launch_bounds__(kBlock) void unpack_sync_kernel(
   }
 
   long long total;
-  const long long mine = block_exclusive_scan(active ? my_blocks : 0, &total);
+  const long long mine =
+      block_exclusive_scan<kBlock>(active ? my_blocks : 0, &total);
   if (active) {
     ws.entry[g * kBlock + tid] = my_in;
     ws.before[g * kBlock + tid] = (uint32_t)mine;
@@ -759,7 +694,7 @@ __global__ __launch_bounds__(kBlock) void unpack_scan_kernel(UnpackLayout ws,
     const int64_t i = base + threadIdx.x;
     long long total;
     const long long before =
-        block_exclusive_scan(i < groups ? ws.blocks[i] : 0, &total);
+        block_exclusive_scan<kBlock>(i < groups ? ws.blocks[i] : 0, &total);
     if (i < groups) ws.first[i] = carry + before;
     carry += total;
   }

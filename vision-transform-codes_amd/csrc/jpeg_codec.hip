@@ -20,6 +20,7 @@
 
 #include "../../include/vtc_codec.h"
 #include "bitstream.h"
+#include "block_scan.h"
 #include "common.h"
 
 namespace vtc {
@@ -34,15 +35,6 @@ constexpr int kDcBase = 256;
 constexpr int kEob = 0x00, kZrl = 0xF0;
 constexpr int kScanItems = 8;
 constexpr int kScanTile = kBlock * kScanItems;
-
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // What lane `lane` of chunk `chunk` contributes to the stream of one row.
 struct LaneToken {
@@ -178,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void stream_bits_kernel(
   }
   over = wave_sum_int(over);
   if (lane == 0 && over) atomicAdd(&status[0], over);
-  missing = wave_min_int(missing);
+  missing = wave_min(missing);
   if (lane == 0 && missing != INT_MAX) atomicMin(&status[1], missing);
 }
 
@@ -257,34 +249,11 @@ __global__ __launch_bounds__(kBlock) void pack_kernel(
   }
   over = wave_sum_int(over + dropped);
   if (lane == 0 && over) atomicAdd(&status[0], over);
-  missing = wave_min_int(missing);
+  missing = wave_min(missing);
   if (lane == 0 && missing != INT_MAX) atomicMin(&status[1], missing);
 }
 
-// ---- offsets: exclusive scan in three steps ---------------------------------
-// Exclusive prefix of `v` over the block's 256 threads; *total = block sum.
-__device__ __forceinline__ long long block_exclusive_scan(long long v,
-                                                          long long* total) {
-  __shared__ long long wave_sums[kWavesPerBlock];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  long long incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wave_sums[wave] = incl;
-  __syncthreads();
-  long long before = 0, all = 0;
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    if (w < wave) before += wave_sums[w];
-    all += wave_sums[w];
-  }
-  __syncthreads();   // wave_sums is reused by the next call
-  *total = all;
-  return before + incl - v;
-}
-
+// ---- offsets: exclusive scan in three steps (block_scan.h) -------------------
 __device__ __forceinline__ long long scan_thread_sum(const int32_t* bits,
                                                      int64_t d, int64_t first) {
   long long sum = 0;
@@ -299,22 +268,14 @@ __global__ __launch_bounds__(kBlock) void scan_tile_sums_kernel(
   const int64_t first =
       (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
   long long total;
-  block_exclusive_scan(scan_thread_sum(bits, d, first), &total);
+  block_exclusive_scan<kBlock>(scan_thread_sum(bits, d, first), &total);
   if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // step 2 (one block): sums[b] = sum of the tiles before b
 __global__ __launch_bounds__(kBlock) void scan_sums_kernel(
     long long* __restrict__ sums, int64_t tiles) {
-  long long carry = 0;
-  for (int64_t base = 0; base < tiles; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const long long v = i < tiles ? sums[i] : 0;
-    long long total;
-    const long long before = block_exclusive_scan(v, &total);
-    if (i < tiles) sums[i] = carry + before;
-    carry += total;
-  }
+  block_prefix_tile_sums<kBlock>(sums, tiles);
 }
 
 // step 3: offsets of tile b, and offsets[d] from the thread that holds row d-1
@@ -324,8 +285,8 @@ __global__ __launch_bounds__(kBlock) void scan_write_kernel(
   const int64_t first =
       (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
   long long total;
-  long long at = sums[blockIdx.x] +
-                 block_exclusive_scan(scan_thread_sum(bits, d, first), &total);
+  long long at = sums[blockIdx.x] + block_exclusive_scan<kBlock>(
+                                        scan_thread_sum(bits, d, first), &total);
   for (int k = 0; k < kScanItems; ++k) {
     const int64_t i = first + k;
     if (i >= d) break;

@@ -12,21 +12,19 @@
 // Three steps per call, all on the caller's stream:
 //   1. levels is zero-filled (rows are sparse: a lane stores its nonzero
 //      levels only, a dense row write would be s * 4 bytes apart across lanes)
-//   2. decode_tables_kernel, one block: left-aligns the at most 272 codewords
-//      to 64 bits, sorts each table, checks neighbours for prefix or equality
-//      and builds a first-level lookup of kLutBits bits per table, into the
-//      caller's workspace
+//   2. decode_tables_kernel, one block: the decode tables of prefix_table.h
+//      for the at most 272 codewords, with a first-level lookup of 10 bits
+//      per table, into the caller's workspace
 //   3. unpack_kernel: the tables go to LDS, every lane walks its row
 //
-// A codeword of at most kLutBits bits is found by one LDS read; a longer one
-// by predecessor search in the sorted array: for a prefix-free code the match
-// is the largest left-aligned codeword <= the window, provided the window
-// really starts with it.
+// A codeword of at most 10 bits is found by one LDS read; a longer one by
+// predecessor search in the sorted array.
 #include <limits.h>
 
 #include "../../include/vtc_decode.h"
 #include "bitstream.h"
 #include "common.h"
+#include "prefix_table.h"
 
 namespace vtc {
 namespace {
@@ -36,15 +34,32 @@ constexpr int kAcSymbols = 256, kDcSymbols = 16;
 constexpr int kSymbols = kAcSymbols + kDcSymbols;   // AC bytes, DC categories
 constexpr int kDcBase = kAcSymbols;
 constexpr int kEob = 0x00, kZrl = 0xF0;
-constexpr int kLutBits = 10;
-constexpr int kLutSize = 1 << kLutBits;
 constexpr int kMaxCodeBits = 64;
 
 // meta word of a codeword: length << 9 | symbol id (ids below 272, lengths
 // 1..64); 0 is no codeword.
-__host__ __device__ constexpr unsigned meta_of(int len, int id) {
-  return (unsigned)len << 9 | (unsigned)id;
-}
+struct JpegCode {
+  typedef u64 Key;
+  typedef uint16_t Meta;
+  static constexpr int kLutBits = 10;
+  static __host__ __device__ constexpr unsigned make(int len, int id) {
+    return (unsigned)len << 9 | (unsigned)id;
+  }
+  static __host__ __device__ constexpr bool valid(unsigned m) {
+    return m != 0;
+  }
+  static __host__ __device__ constexpr int len(unsigned m) {
+    return m >> 9;
+  }
+  static __host__ __device__ constexpr int symbol(unsigned m) {
+    return m & 511;
+  }
+};
+typedef PrefixTable<JpegCode> Table;
+constexpr int kLutSize = Table::kLutSize;
+static_assert(Table::round_trips(1, 0) && Table::round_trips(64, 0) &&
+                  Table::round_trips(1, 271) && Table::round_trips(64, 271),
+              "length << 9 | id");
 
 struct DecodeLayout {
   u64* code;        // [272] left-aligned, sorted: AC from 0, DC from 256
@@ -59,89 +74,50 @@ struct DecodeLayout {
   }
 };
 
-// ---- table preparation ------------------------------------------------------
-// (key, length, id) order; entries of length 0 are not compared at all.
-__device__ __forceinline__ bool sorts_before(u64 ka, int la, int ia, u64 kb,
-                                             int lb, int ib) {
-  if (ka != kb) return ka < kb;
-  if (la != lb) return la < lb;
-  return ia < ib;
-}
-
+// ---- table preparation (prefix_table.h) -------------------------------------
 __global__ __launch_bounds__(kBlock) void decode_tables_kernel(
     const u64* __restrict__ ac_code, const uint8_t* __restrict__ ac_len,
     const u64* __restrict__ dc_code, const uint8_t* __restrict__ dc_len,
     DecodeLayout ws, u64* __restrict__ status) {
-  __shared__ u64 key[kSymbols], sorted_key[kSymbols];
-  __shared__ uint8_t len[kSymbols];
-  __shared__ uint16_t sorted_meta[kSymbols];
+  __shared__ u64 key[kSymbols];
+  __shared__ uint16_t meta[kSymbols];
   __shared__ uint16_t lut[2 * kLutSize];
   __shared__ int count[2], bad;
   const int tid = threadIdx.x;
   if (tid < 2) count[tid] = 0;
   if (tid == 0) bad = INT_MAX;
+  for (int i = tid; i < 2 * kLutSize; i += kBlock) lut[i] = 0;
+  __syncthreads();
   for (int i = tid; i < kSymbols; i += kBlock) {
     int l = i < kDcBase ? ac_len[i] : dc_len[i - kDcBase];
     if (l > kMaxCodeBits) l = kMaxCodeBits;
     const u64 c = i < kDcBase ? ac_code[i] : dc_code[i - kDcBase];
-    len[i] = (uint8_t)l;
-    key[i] = l ? c << (kMaxCodeBits - l) : 0;   // bits above `l` fall off
-    sorted_key[i] = 0;
-    sorted_meta[i] = 0;
-  }
-  for (int i = tid; i < 2 * kLutSize; i += kBlock) lut[i] = 0;
-  __syncthreads();
-
-  // rank sort, each table on its own
-  for (int i = tid; i < kSymbols; i += kBlock) {
-    if (!len[i]) continue;
-    const int table = i >= kDcBase;
-    const int base = table ? kDcBase : 0;
-    const int n = table ? kDcSymbols : kAcSymbols;
-    int rank = 0;
-    for (int j = base; j < base + n; ++j)
-      if (len[j] && sorts_before(key[j], len[j], j, key[i], len[i], i)) ++rank;
-    sorted_key[base + rank] = key[i];
-    sorted_meta[base + rank] = (uint16_t)meta_of(len[i], i);
-    atomicAdd(&count[table], 1);
+    key[i] = Table::left_align(c, l);
+    meta[i] = l ? JpegCode::make(l, i) : 0;
+    if (l) atomicAdd(&count[i >= kDcBase], 1);
   }
   __syncthreads();
+  Table::sort<kBlock>(key, meta, kAcSymbols);   // each table on its own
+  Table::sort<kBlock>(key + kDcBase, meta + kDcBase, kDcSymbols);
 
-  // If a codeword is a prefix of any other, it is one of its successor in
-  // sorted order: neighbours suffice.
   for (int i = tid; i < kSymbols; i += kBlock) {
     const int table = i >= kDcBase;
     const int r = i - (table ? kDcBase : 0);
     if (r + 1 >= count[table]) continue;
-    const u64 a = sorted_key[i], b = sorted_key[i + 1];
-    const int la = sorted_meta[i] >> 9, lb = sorted_meta[i + 1] >> 9;
-    if (la <= lb && ((a ^ b) >> (kMaxCodeBits - la)) == 0) {
-      atomicMin(&bad, (int)(sorted_meta[i] & 511));
-      if (la == lb) atomicMin(&bad, (int)(sorted_meta[i + 1] & 511));
-    }
+    const int offender = Table::prefix_violation(key, meta, i);
+    if (offender != INT_MAX) atomicMin(&bad, offender);
   }
   __syncthreads();
-
-  // first level: every kLutBits-bit prefix that starts with a short codeword.
-  // The code is prefix-free here, so the ranges of two codewords are disjoint.
-  if (bad == INT_MAX) {
-    for (int i = tid; i < kSymbols; i += kBlock) {
-      const int table = i >= kDcBase;
-      const int r = i - (table ? kDcBase : 0);
-      if (r >= count[table]) continue;
-      const int l = sorted_meta[i] >> 9;
-      if (l > kLutBits) continue;
-      const int first = (int)(sorted_key[i] >> (kMaxCodeBits - kLutBits));
-      const int span = 1 << (kLutBits - l);
-      for (int q = 0; q < span; ++q)   // first + span <= kLutSize
-        lut[table * kLutSize + first + q] = sorted_meta[i];
-    }
+  if (bad == INT_MAX) {   // prefix-free: the ranges are disjoint
+    Table::fill_lookup(lut, key, meta, count[0], tid, kBlock);
+    Table::fill_lookup(lut + kLutSize, key + kDcBase, meta + kDcBase, count[1],
+                       tid, kBlock);
   }
   __syncthreads();
 
   for (int i = tid; i < kSymbols; i += kBlock) {
-    ws.code[i] = sorted_key[i];
-    ws.meta[i] = sorted_meta[i];
+    ws.code[i] = key[i];
+    ws.meta[i] = meta[i];
   }
   for (int i = tid; i < 2 * kLutSize; i += kBlock) ws.lut[i] = lut[i];
   if (tid == 0) {
@@ -162,37 +138,13 @@ __global__ void unpack_end_kernel(u64* status) {
 
 // BitReader, the bit reader of one lane: bitstream.h
 
-// The codeword the window starts with, as a meta word; 0 when none does.
-// lut, code, meta: one table's arrays in LDS; n: its codewords.
-__device__ __forceinline__ unsigned match(const uint16_t* lut, const u64* code,
-                                          const uint16_t* meta, int n, u64 w) {
-  const unsigned e = lut[w >> (kMaxCodeBits - kLutBits)];
-  if (e) return e;
-  int lo = 0, hi = n;   // lo: number of codewords <= w
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (code[mid] <= w)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  if (lo == 0) return 0;
-  const unsigned m = meta[lo - 1];
-  if ((code[lo - 1] ^ w) >> (kMaxCodeBits - (m >> 9))) return 0;
-  return m;
-}
-
 // Reads one codeword of a table: its symbol id, or -1 (no match, or the match
 // passes the row's end or the buffer).
 __device__ __forceinline__ int read_symbol(BitReader& r, const uint16_t* lut,
                                            const u64* code,
                                            const uint16_t* meta, int n) {
-  r.refill();
-  const unsigned m = match(lut, code, meta, n, r.window64());
-  const int l = m >> 9;
-  if (!m || l > r.avail64()) return -1;
-  r.consume(l);
-  return m & 511;
+  const unsigned m = Table::read(r, lut, code, meta, n);
+  return m ? JpegCode::symbol(m) : -1;
 }
 
 // Reads `size` value bits, 1..15; false when they pass the end.
